@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — env-steps/s of the batched step() hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--env rock|tag|battleship|tiger|network]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--env rock|tag|battleship|tiger|network] [--dump-outputs DIR]
 
 Workload (BASELINE.json metric): RockSample(7,8), 2^20 lanes per GPU, i.i.d. uniform random
 actions from the synthetic policy (its kernel is inside the timed region), auto-reset on done.
@@ -202,6 +202,10 @@ def parse():
                     help="allow fewer visible GPUs than ranks (ranks then share devices: a development aid, e.g. two ranks on a "
                          "one-GPU box); without it such a run is an error, so a line that says n_gpus: N ran on N GPUs")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline sample")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step (the arrays its caller "
+                         "receives, and the lanes' state) as DIR/<name>.npy, float32 / float64, at most 64 MB in all: the same "
+                         "arguments give the same inputs on every run, so two builds can be compared output for output")
     return ap.parse_args()
 
 
@@ -211,6 +215,38 @@ def prewarm(args, run, dev, k=64):
     while time.perf_counter() - t0 < args.prewarm:
         run(k)
         torch.cuda.synchronize(dev)
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, rank=0, world=1):
+    """--dump-outputs: `arrays` (name -> tensor, lanes on the last axis) as <path>/<name>.npy — float64 for 32- and 64-bit
+    values (exact for int32, and for the state's words read as uint32), float32 for narrower ones and float32 itself.  Over
+    DUMP_BYTES in all (DUMP_BYTES / world per rank), a fixed seeded sample of the lanes is written instead, its lane
+    indices in lane_index.npy.  N > 1: every rank writes its own shard, the file names ending in _rank<r>."""
+    import numpy as np
+    host = {}
+    for k, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        if k == "state":
+            a = a.view(np.uint32).astype(np.float64)
+        elif a.dtype == np.float32 or a.dtype == np.bool_ or a.itemsize < 4:
+            a = a.astype(np.float32)
+        else:
+            a = a.astype(np.float64)
+        host[k] = a
+    n = next(iter(host.values())).shape[-1]
+    total, budget = sum(a.nbytes for a in host.values()), DUMP_BYTES // world - 4096 * (len(host) + 1)     # (+ .npy headers)
+    if total > budget:
+        keep = int(budget // (total / n + 8))
+        idx = np.sort(np.random.RandomState(0).choice(n, keep, replace=False))
+        host = {k: np.ascontiguousarray(a[..., idx]) for k, a in host.items()}
+        host["lane_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    suffix = "" if world == 1 else "_rank%d" % rank
+    for k, a in host.items():
+        np.save(os.path.join(path, k + suffix + ".npy"), a)
 
 
 def median(xs):
@@ -366,7 +402,9 @@ def rollout_mode(args, env, cp, dev, rank, world, label):
                 total.add_(r["n_steps"].sum())
 
     args.prewarm = max(args.prewarm, 3.0)     # a compute-only kernel: the first seconds after idle run at ~half speed
+    t_start = env.call_counter
     prewarm(args, lambda k: run(k, True), dev)        # with the step count's reduction in: its first launches are slow too
+    env.call_counter = t_start                        # the prewarm runs for a time, not a count: same launches after it on every run
     run(args.warmup, True)
     torch.cuda.synchronize(dev)
     total.zero_()
@@ -380,6 +418,8 @@ def rollout_mode(args, env, cp, dev, rank, world, label):
     elapsed = cp.max(time.perf_counter() - t0)
     cp.barrier()
     launch_ms = ev0.elapsed_time(ev1) / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, bufs[0], rank, world)
     steps_done = cp.sum(int(total.item()))
     # a fused rollout moves next to nothing — the root's state words in, 21 B of results out per
     # simulation of up to `depth` steps — so the HBM figure only shows how far from memory-bound it is; what bounds
@@ -423,12 +463,13 @@ def heuristic_mode(args, gpa, env_id, kwargs, cp, dev, rank, world, label, n, la
         return e, gpa.History(e)
 
     chunk = fuse_max()
+    last = [None]
 
     def stepper(e, h):
         def run(k):
             while k > 0:
                 c = min(k, chunk)            # whole launches of pomdp_fuse_max() steps
-                e.heuristic_steps(h, c)
+                last[0] = e.heuristic_steps(h, c)
                 k -= c
         return run
 
@@ -455,6 +496,8 @@ def heuristic_mode(args, gpa, env_id, kwargs, cp, dev, rank, world, label, n, la
     elapsed = cp.max(time.perf_counter() - t0)
     cp.barrier()
     kern_ms = ev0.elapsed_time(ev1) / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(zip(("action", "ob", "reward", "done"), last[0]), state=env.state), rank, world)
     # algorithmic bytes per lane-step: with many steps per launch the lane's state and history words
     # stay in registers, so a step must write action, ob, reward, done = 13 B; state in / out once per launch (a CHECK's
     # statistics update — one rock's five fields and two sums — is not counted, nor the 40 B of history words per lane
@@ -751,7 +794,7 @@ class StepWorkload(object):
         self.chained = args.host_loop == "c" and self.shared_key
         self.fused = self.chained and bool(args.fuse)
         self.views = {}
-        self.stats = self.cols = None
+        self.stats = self.cols = self.last = None
         if self.collect:
             # one [CHUNK + 1][n] trajectory buffer per column; a call of c steps writes the first c (+ 1) rows
             c = min(self.CHUNK, max(args.steps, args.warmup, max_steps, 1))
@@ -785,6 +828,8 @@ class StepWorkload(object):
     def reseed(self, seed):
         self.env.seed(seed)
         self.env.reset()
+        if self.stats is not None:
+            self.stats.reset()
 
     def action_seed(self):
         return self.env._seed if self.shared_key else self.args.action_seed
@@ -801,15 +846,38 @@ class StepWorkload(object):
                     if self.cols is not None:
                         env.decode_trajectory(self._view(c), into=self.cols)
                 left -= c
+                self.last = c
         elif self.args.host_loop == "python":
             for _ in range(k):
                 env.synthetic_actions(out=self.actions, seed=self.action_seed())
-                env.step(self.actions)
+                self.last = env.step(self.actions)[:3]
         else:
             while left > 0:
                 c = min(left, self.CHUNK)
-                env.rollout_synthetic(c, action_seed=self.action_seed(), actions=self.actions, fuse=self.fused)
+                self.last = env.rollout_synthetic(c, action_seed=self.action_seed(), actions=self.actions, fuse=self.fused)
                 left -= c
+
+    def outputs(self):
+        """What a caller of run() holds after its last step (--dump-outputs): that step's action / ob / reward / done rows
+        (the returns sink: the lanes' episode statistics instead), and the lanes' state."""
+        env = self.env
+        if self.stats is not None:
+            s = self.stats
+            out = {"ret": s.ret, "disc": s.disc, "ret_done": s.ret_done, "ret_sum": s.ret_sum, "episodes": s.episodes, "steps": s.steps}
+        elif self.collect:
+            c = self.last
+            if self.cols is not None:                   # packed_plus_decode: the columns the records were decoded into
+                tr = {k: self.cols[k][:c] for k in ("action", "ob", "reward", "done")}
+            else:                                       # the last row alone (decoding a whole launch's records would copy GBs)
+                v = self._view(c)
+                tr = env.decode_trajectory(v if "layout" not in v else dict(v, traj=v["traj"][c - 1:c]))
+            out = {k: tr[k][-1] for k in ("action", "ob", "reward", "done")}
+        else:
+            out = dict(zip(("ob", "reward", "done"), self.last))
+            if self.args.host_loop == "python":
+                out["action"] = self.actions
+        out["state"] = env.state
+        return out
 
     def measure(self, seeds, cp):
         """The §8d protocol.  -> (per-seed [(seed, median wall s, min, max, median event ms)])."""
@@ -820,6 +888,7 @@ class StepWorkload(object):
             self.reseed(seed)
             if i == 0:
                 prewarm(args, self.run, self.dev, k)      # same chunking as the timed region: every row it writes is touched
+                self.reseed(seed)                          # it runs for a time, not a count: the steps after it are the same on every run
             self.run(args.warmup)
             self.run(k)                                    # untimed pass over exactly the timed call sequence
             walls, evs = timed_regions(self.run, k, repeats, self.dev, cp)
@@ -871,6 +940,8 @@ def main():
     wl = StepWorkload(args, gpa, env_id, kwargs, dev, n, lane_offset, seeds[0])
     env = wl.env
     rows, repeats = wl.measure(seeds, cp)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, wl.outputs(), rank, world)
     elapsed = median([r[1] for r in rows])
     timed_kernel_ms = median([r[4] for r in rows]) / args.steps
     fused_kernel = _native.lib().pomdp_last_fused_kernel().decode() if wl.fused else None

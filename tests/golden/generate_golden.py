@@ -13,6 +13,9 @@ Fixtures:
   F3  modeB_<case>.npz   reference driven by the build's Philox word stream
                          (per-lane env objects; includes F4 = initial resets)
   F5  edge_cases.json    error behaviour of the reference at the boundary
+      live_<id>.npz      modes A and B on seeds drawn once, in configurations
+                         of no other fixture (tests/test_reference_live.py;
+                         --live-only writes these alone)
 """
 import json
 import os
@@ -245,6 +248,39 @@ def gen_heuristic(case, env, kwargs, L, T, max_size=None):
     return int(tr["done"].sum()), float(tr["pref_len"].mean()), tries
 
 
+# tests/test_reference_live.py: configurations of no other fixture, on seeds / lanes / counters drawn once (fixed draws here,
+# so that the fixtures are reproducible): live_<id>.npz, <id> the test's parameter id
+LIVE_CASES = [("rock", {}), ("rock", dict(board_size=11, num_rocks=11)), ("stochrock", {}), ("tag", {}),
+              ("tag", dict(num_opponents=3)), ("tag", dict(move_prob=.3)), ("tag", dict(num_opponents=2, move_prob=.55)), ("battleship", {}),
+              ("battleship", dict(board_size=(7, 9), max_len=4)), ("tiger", {}), ("network", {}),
+              ("network", dict(n_machines=13, problem_type=3)), ("network", dict(n_machines=7, problem_type=2))]
+LIVE_MODE_A = (4, 400)            # seeds, steps per seed
+LIVE_MODE_B = (2, 12, 40)         # draws of (seed, lane0, t0), lanes, steps per draw
+
+
+def gen_live(i, env, kwargs):
+    nA = n_actions(env, kwargs)
+    rs = np.random.RandomState(0x11FE + i)
+    out = {"env": np.str_(env), "kwargs": np.str_(json.dumps({k: (list(v) if isinstance(v, tuple) else v) for k, v in kwargs.items()}, sort_keys=True))}
+    for j in range(LIVE_MODE_A[0]):
+        seed = int(rs.randint(0, 2 ** 31))
+        acts = action_tape(env, nA, rs, LIVE_MODE_A[1])
+        tr = h.trace_mode_a(env, kwargs, seed, acts)
+        out.update({"a%d_seed" % j: np.int64(seed), "a%d_actions" % j: np.asarray(acts, np.int64)})
+        out.update({"a%d_%s" % (j, k): np.asarray(tr[k]) for k in ("ob", "reward", "done", "state_pre", "state", "reset_ob")})
+    n_b, L, T = LIVE_MODE_B
+    for j in range(n_b):
+        seed, lane0, t0 = int(rs.randint(0, 2 ** 62)), int(rs.randint(0, 2 ** 31)), int(rs.randint(0, 2 ** 40))
+        acts = rs.randint(nA, size=(L, T))
+        tr = h.trace_mode_b(env, kwargs, seed, range(lane0, lane0 + L), acts, t0=t0)
+        out.update({"b%d_seed" % j: np.uint64(seed), "b%d_lane0" % j: np.int64(lane0), "b%d_t0" % j: np.int64(t0),
+                    "b%d_actions" % j: acts.astype(np.int64)})
+        out.update({"b%d_%s" % (j, k): np.asarray(tr[k]) for k in ("ob0", "ob", "reward", "done", "state")})
+    name = "live_%s-%d.npz" % (env, i)
+    np.savez_compressed(os.path.join(HERE, name), **out)
+    return name, sum(int(out["a%d_done" % j].sum()) for j in range(LIVE_MODE_A[0])), sum(int(out["b%d_done" % j].sum()) for j in range(n_b))
+
+
 def gen_thresholds():
     def binom_at(p, k):
         h.inject_words([(k >> 26) << 5, (k & ((1 << 26) - 1)) << 6])
@@ -343,6 +379,10 @@ def main():
     assert h.reference_available(), "needs /root/reference"
     import warnings
     warnings.simplefilter("ignore", RuntimeWarning)  # reference's belief side-stats divide 0/0 (rock.py:191)
+    if "--live-only" in sys.argv:
+        for i, (env, kwargs) in enumerate(LIVE_CASES):
+            print("live %-22s modeA dones=%4d  modeB dones=%4d" % gen_live(i, env, kwargs), flush=True)
+        return
     gen_thresholds()
     if "--bounded-history-only" in sys.argv:
         for case, env, kwargs, L, T, ms in HEUR_BOUNDED:
@@ -396,6 +436,9 @@ def main():
             continue
         tr = gen_plan(case, env, kwargs, R, S, depth)
         print("plan %-16s best=%s" % (case, tr["best"].tolist()), flush=True)
+    if not only:
+        for i, (env, kwargs) in enumerate(LIVE_CASES):
+            print("live %-22s modeA dones=%4d  modeB dones=%4d" % gen_live(i, env, kwargs), flush=True)
     write_manifest()
 
 

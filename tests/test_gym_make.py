@@ -82,11 +82,29 @@ print("child ok")
 """, GYM_STUB)
 
 
-def test_the_reference_registered_first_keeps_its_ids():
+# A stand-in for the reference package as gym sees it: a `gym_pomdp` whose import registers the ids this package registers too,
+# each to a class of its own modules (gym_pomdp/__init__.py, gym_pomdp/envs/*.py of d3sm0/gym_pomdp)
+REFERENCE_IDS = {"Tiger-v0": ("tiger", "TigerEnv"), "Tag-v0": ("tag", "TagEnv"), "Battleship-v0": ("battleship", "BattleShipEnv"),
+                 "Rock-v0": ("rock", "RockEnv"), "StochasticRock-v0": ("rock", "StochasticRockEnv"), "Network-v0": ("network", "NetworkEnv")}
+
+
+def reference_stand_in(root):
+    pkg = root / "gym_pomdp"
+    (pkg / "envs").mkdir(parents=True)
+    (pkg / "__init__.py").write_text("from gym.envs.registration import register\n" + "".join(
+        "register(id=%r, entry_point=%r)\n" % (i, "gym_pomdp.envs:" + c) for i, (_, c) in REFERENCE_IDS.items()))
+    mods = {}
+    for m, c in REFERENCE_IDS.values():
+        mods.setdefault(m, []).append(c)
+    for m, classes in mods.items():
+        (pkg / "envs" / (m + ".py")).write_text("import gym\n" + "".join("class %s(gym.Env):\n    pass\n" % c for c in classes))
+    (pkg / "envs" / "__init__.py").write_text("".join("from gym_pomdp.envs.%s import %s\n" % (m, c) for m, c in REFERENCE_IDS.values()))
+    return str(root)
+
+
+def test_the_reference_registered_first_keeps_its_ids(tmp_path):
     """Both packages imported in one process (the parity harness does that): the reference's registrations stay, ours are
     skipped without an exception; any error other than gym's own re-registration error propagates."""
-    if not os.path.isdir("/root/reference/gym_pomdp"):
-        pytest.skip("needs /root/reference")
     run_child("""
 import gym, gym_pomdp
 import gym_pomdp_amd as gpa
@@ -108,7 +126,7 @@ except ValueError:
     pass
 reg.register = orig
 print("child ok")
-""", GYM_STUB, "/root/reference")
+""", GYM_STUB, reference_stand_in(tmp_path))
 
 
 def test_gymnasium_make_gets_a_gymnasium_env():

@@ -198,7 +198,7 @@ def test_stream_and_device_handles_fall_back_to_the_public_api():
     assert src.count("torch._C") == 1, "private torch internals are touched in _resolve_fast_handles only"
 
 
-def test_fused_step_loops_never_wait_for_their_own_stores():
+def test_fused_step_loops_never_wait_for_their_own_stores(tmp_path):
     """Static property of the compiled kernels (tools/check_loop_waits.py, no GPU needed): inside the step loop of the
     headline kernel and of its small-shard sibling there is no `s_waitcnt vmcnt` — gfx9 counts loads and stores on one
     counter, so such a wait would stall every step on the previous step's stores — and the priority ladder (LoopPrio:
@@ -206,7 +206,7 @@ def test_fused_step_loops_never_wait_for_their_own_stores():
     import sys
     sys.path.insert(0, os.path.join(REPO, "tools"))
     import check_loop_waits as clw
-    res = clw.loop_waits(clw.assembly("fused_rock.hip"))
+    res = clw.loop_waits(clw.assembly("fused_rock.hip", out_dir=str(tmp_path)))
     seen = taped = taped_small = 0
     for name, (waits, prio) in res.items():
         if "steps_quad_kernel<pomdp::RockEnv<1, false>, " in name or "steps_kernel<pomdp::RockEnv<1, false>, 1, true, true, " in name:
@@ -298,3 +298,34 @@ def test_recorded_counters_belong_to_this_tree():
     assert bench.counters_stale(pmc, "no_such_workload")
     t, _ = bench.recorded_traffic("rock", "packed", 20, "steps_quad_kernel<")
     assert t is not None and 0.9 < t / (4.4 * (1 << 20) * 20) < 1.25, t
+
+
+def test_bench_dump_outputs_are_float_and_fit_64_mb(tmp_path):
+    """bench.py --dump-outputs: every array as float32 / float64 holding the exact values (state words as uint32), at most
+    64 MB in all; above that, the same seeded sample of lanes on every run, its indices in lane_index.npy."""
+    import sys
+    import torch
+    sys.path.insert(0, REPO)
+    import bench
+    n = 1 << 20
+    g = torch.Generator().manual_seed(0)
+    arrays = {"action": torch.randint(0, 13, (n,), dtype=torch.int32, generator=g), "reward": torch.randn(n, generator=g),
+              "done": torch.rand(n, generator=g) < .1, "state": torch.randint(-2 ** 31, 2 ** 31 - 1, (6, n), dtype=torch.int32, generator=g)}
+    small = {k: v[..., :1000] for k, v in arrays.items()}
+    bench.dump_outputs(str(tmp_path / "small"), small)
+    got = {k: np.load(str(tmp_path / "small" / (k + ".npy"))) for k in small}
+    assert sorted(os.listdir(str(tmp_path / "small"))) == sorted(k + ".npy" for k in small)
+    assert got["action"].dtype == np.float64 and got["reward"].dtype == np.float32 and got["done"].dtype == np.float32
+    assert np.array_equal(got["state"], small["state"].numpy().view(np.uint32).astype(np.float64))
+    assert np.array_equal(got["reward"], small["reward"].numpy()) and np.array_equal(got["done"], small["done"].numpy())
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays)
+        d = tmp_path / run
+        assert sum(os.path.getsize(str(d / f)) for f in os.listdir(str(d))) <= 64 << 20
+    idx = np.load(str(tmp_path / "a" / "lane_index.npy"))
+    assert idx.dtype == np.float64 and 0 < len(idx) < n and (np.diff(idx) > 0).all()
+    for k, v in arrays.items():
+        a, b = np.load(str(tmp_path / "a" / (k + ".npy"))), np.load(str(tmp_path / "b" / (k + ".npy")))
+        assert np.array_equal(a, b) and a.dtype in (np.float32, np.float64)
+        want = v.numpy().view(np.uint32) if k == "state" else v.numpy()
+        assert np.array_equal(a, want[..., idx.astype(np.int64)].astype(a.dtype))
