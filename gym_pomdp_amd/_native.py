@@ -16,17 +16,18 @@ INTREE_LIB_PATH = os.path.join(_PKG, "_lib", "libpomdp_hip.so")
 LIB_PATH = os.environ.get("GYM_POMDP_AMD_LIB") or INTREE_LIB_PATH
 # one object per translation unit (built in parallel), linked into one shared library
 UNITS = ["api.hip", "step_rock.hip", "step_other.hip", "fused_rock.hip", "fused_stochrock.hip", "fused_tag.hip",
-         "fused_battleship.hip", "fused_misc.hip", "planner.hip"]
+         "fused_battleship.hip", "fused_misc.hip", "planner.hip", "episodes.hip"]
 HEADERS = ["kernels_common.hip.h", "traj_out.hip.h", "step_impl.hip.h", "fused_impl.hip.h", "envs.hip.h", "envs_common.hip.h", "philox.hip.h",
            "envs/rock.hip.h", "envs/tag.hip.h", "envs/battleship.hip.h", "envs/tiger.hip.h", "envs/network.hip.h"]
 SOURCES = [os.path.join(_PKG, "csrc", f) for f in UNITS + HEADERS]
 HEADER = os.path.join(_REPO, "include", "pomdp_hip.h")
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 POMDP_AUTO_RESET = 1
 POMDP_FUSE_STEPS = 2
 POMDP_ROLLOUT_ALL_ACTIONS = 1
 LAYOUTS = {"columns": 0, "blocked": 1, "packed": 2, "narrow": 3}     # POMDP_LAYOUT_*
+POMDP_LAYOUT_RETURNS = 4                                              # pomdp_finish_episodes only
 FUSE_MAX_DEFAULT = 256
 ENV_KIND = {"rock": 0, "tag": 1, "battleship": 2, "tiger": 3, "network": 4}
 
@@ -39,6 +40,7 @@ SYMBOLS = [
     "pomdp_rollout_synthetic", "pomdp_collect_synthetic", "pomdp_collect", "pomdp_collect_layout", "pomdp_collect_traj", "pomdp_packed_reward", "pomdp_decode_packed", "pomdp_collect_returns", "pomdp_collect_tape", "pomdp_collect_tape_layout", "pomdp_collect_tape_returns", "pomdp_fuse_max", "pomdp_fuse_steps", "pomdp_legal_actions", "pomdp_rollout", "pomdp_plan", "pomdp_plan_reduce", "pomdp_compute_prob",
     "pomdp_rock_belief_reset", "pomdp_rock_belief_refresh", "pomdp_rock_belief_update", "pomdp_rock_select_target", "pomdp_history_clear",
     "pomdp_history_append", "pomdp_preferred_actions", "pomdp_pick_actions", "pomdp_heuristic_steps",
+    "pomdp_reset_where", "pomdp_finish_episodes",
 ]
 
 
@@ -101,6 +103,12 @@ class ReturnStats(C.Structure):     # pomdp_return_stats
 
 class Tape(C.Structure):            # pomdp_tape
     _fields_ = [("actions", C.c_void_p), ("stride", C.c_int64)]
+
+
+class EpisodeArgs(C.Structure):     # pomdp_episode_args
+    _fields_ = [("env", C.c_int32), ("layout", C.c_int32), ("params", C.c_void_p), ("state", C.c_void_p), ("done", C.c_void_p),
+                ("tape", C.c_void_p), ("traj", C.c_void_p), ("pitch", C.c_int64), ("stats", C.c_void_p), ("err", C.c_void_p),
+                ("n", C.c_int64), ("seed", C.c_uint64), ("lane0", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class PlanOut(C.Structure):         # pomdp_plan_out
@@ -249,6 +257,10 @@ def lib():
     L.pomdp_pick_actions.argtypes = [vp, vp, ci, vp, i64, u64, u32, u64, vp]
     L.pomdp_heuristic_steps.restype = ci
     L.pomdp_heuristic_steps.argtypes = [ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, u64, u32, u64, i64, ci, vp]
+    L.pomdp_reset_where.restype = ci
+    L.pomdp_reset_where.argtypes = [ci, vp, vp, vp, vp, vp, i64, u64, u32, u64, vp]
+    L.pomdp_finish_episodes.restype = ci
+    L.pomdp_finish_episodes.argtypes = [vp, u64, i64, vp]
     L.pomdp_philox_blocks.restype = ci
     L.pomdp_philox_blocks.argtypes = [vp, vp, i64, vp]
     _lib = L

@@ -217,14 +217,19 @@ class BatchedEnv(compat.EnvBase):
         """hipStream_t of torch's current stream on this env's device (the raw handle: no Stream object is built)."""
         return _raw_stream(self._dev_index)
 
-    def reset(self, *, seed=None, options=None, return_info=False):
+    def reset(self, *, seed=None, options=None, return_info=False, where=None):
         """All lanes start a new episode.  Returns ob: int32[N] tensor (python int if batch_size == 1).
         The reference's reset() takes no arguments; the keywords are what gym 0.22-0.25's `gym.make` wrappers pass through
-        (`seed`: seed(seed) first; `return_info`: (ob, info) instead of ob; `options` is accepted and ignored)."""
+        (`seed`: seed(seed) first; `return_info`: (ob, info) instead of ob; `options` is accepted and ignored).
+        `where` (bool / uint8 [N], e.g. env.done): only those lanes start a new episode — the one reset() at this call counter
+        would give them — and have their done flag cleared; every other lane keeps its state and done flag and reports
+        ob = -1 (pomdp_reset_where).  The call counter advances by one either way."""
         if seed is not None:
             self.seed(seed)
         if return_info:
-            return self.reset(), self._info
+            return self.reset(where=where), self._info
+        if where is not None:
+            return self._reset_where(where)
         t = self._t
         self._t += 1
         if self.batch_size == 1 and not self._dev_flags_used and _current_device() == self._dev_index:
@@ -260,6 +265,48 @@ class BatchedEnv(compat.EnvBase):
         if self.batch_size == 1:
             return int(ob.item())
         return ob
+
+    def _reset_where(self, where):
+        """reset(where=...): the masked reset of the lanes with where[i] != 0."""
+        if not self._has_reset:
+            raise AttributeError("%s: reset(where=...) before reset()" % type(self).__name__)
+        n = self.batch_size
+        if n == 1:
+            w = where.item() if isinstance(where, torch.Tensor) else np.asarray(where).reshape(-1)[0]
+            if bool(w):
+                return self.reset()
+            self._t += 1
+            return -1
+        mask = self._as_lane_mask(where)
+        t = self._t
+        self._t += 1
+        with torch.cuda.device(self.device):
+            ob = self._ob if self.reuse_buffers else torch.empty_like(self._ob)
+            rc = self._lib.pomdp_reset_where(self._step_args.env, self._params_ref, self._ptrs[0], ob.data_ptr(), self._ptrs[3],
+                                             mask.data_ptr(), n, self._seed, self.lane_offset, t, self._stream())
+            _native.check(rc, "pomdp_reset_where")
+            if self._tracker is not None:
+                self._tracker.on_reset(mask)
+        self._last_reset = None         # not every lane's observation is a fresh episode's
+        self.done = self._done.view(torch.bool)
+        return ob
+
+    def _as_lane_mask(self, where):
+        """a per-lane mask (bool / integer [N], any device) as the uint8 tensor on this env's device the kernels read"""
+        if isinstance(where, torch.Tensor):
+            if where.dtype.is_floating_point:
+                raise AssertionError("a lane mask must be bool or integer")
+            m = where.to(self.device)
+        else:
+            arr = np.asarray(where)
+            if arr.dtype.kind not in "biu":
+                raise AssertionError("a lane mask must be bool or integer")
+            m = torch.as_tensor(arr, device=self.device)
+        if m.shape != (self.batch_size,):
+            raise AssertionError("a lane mask must have shape (%d,), got %s" % (self.batch_size, tuple(m.shape)))
+        if m.dtype != torch.uint8:
+            m = (m != 0).to(torch.uint8)
+        return m.contiguous()
 
     def step(self, action):
         """action: int32[N] tensor on this env's device (other integer tensors / arrays / lists are
@@ -840,6 +887,66 @@ class BatchedEnv(compat.EnvBase):
                                                      _native.POMDP_AUTO_RESET, self._stream())
             _native.check(rc, "pomdp_collect_tape_layout")
         return out
+
+    def finish_episodes(self, steps, actions=None, layout="returns", out=None, stats=None):
+        """Play the batch's episodes on: `steps` consecutive step() calls of an auto_reset=False env in one fused loop
+        (pomdp_finish_episodes) — the synthetic uniform policy, or the CALLER's actions (`actions`: [steps, N], as_tape rules;
+        steps = len(actions)).  A lane whose episode has ended (env.done) is frozen: it does not step, and every row of it
+        reports (ob, reward, done) = (0, 0, 1), as step() does; env.done is updated in place.
+        layout "returns" (default, or `stats` given): the episode statistics of collect_returns booked for live steps only —
+        from a fresh EpisodeStats after reset(), stats.ret_done[i] is lane i's discounted return and stats.steps[i] its length;
+        returns the EpisodeStats.  "packed" / "narrow": the trajectory (trajectory_buffers; decode_trajectory works), frozen
+        rows padded; returns the dict.  `out` / `stats` continue an earlier call.  Then reset(where=env.done) restarts the
+        finished lanes.  auto_reset=False envs only.  Asynchronous: there is no early stop on the host."""
+        if not self._has_reset:
+            raise AttributeError("%s: finish_episodes before reset()" % type(self).__name__)
+        if self.auto_reset:
+            raise ValueError("finish_episodes needs auto_reset=False (an auto-reset env never finishes)")
+        self._check_driver_use("finish_episodes")
+        n = self.batch_size
+        if n == 1:
+            raise ValueError("finish_episodes: a batch of one keeps its done flag on the host — use step()")
+        if stats is not None:
+            layout = "returns"
+        elif out is not None:
+            layout = out.get("layout", "columns")
+        if layout not in ("returns", "packed", "narrow"):
+            raise ValueError("finish_episodes: layout must be 'returns', 'packed' or 'narrow', got %r" % (layout,))
+        tape = ct = None
+        if actions is not None:
+            tape = self.as_tape(actions)
+            steps = tape.shape[0]
+            ct = _native.Tape(actions=tape.data_ptr(), stride=tape.stride(0) if steps > 1 else max(tape.stride(0), n))
+        steps = int(steps)
+        args = _native.EpisodeArgs(env=_native.ENV_KIND[self.env_name], layout=0, params=C.addressof(self._params),
+                                   state=self._ptrs[0], done=self._ptrs[3], tape=C.addressof(ct) if ct is not None else None,
+                                   traj=None, pitch=0, stats=None, err=self._ptrs[4], n=n, seed=self._seed,
+                                   lane0=self.lane_offset, reserved=0)
+        with torch.cuda.device(self.device):
+            if layout == "returns":
+                if stats is None:
+                    from ..history import EpisodeStats
+                    stats = EpisodeStats(self)
+                elif stats._n != n or stats.acc.device != self.device:
+                    raise ValueError("finish_episodes: `stats` belongs to another batch")
+                args.layout, args.stats = _native.POMDP_LAYOUT_RETURNS, C.addressof(stats._ptrs)
+                result = stats
+            else:
+                if out is None:
+                    out = self.trajectory_buffers(steps, layout)
+                traj, pitch = out["traj"], int(out["pitch"])
+                row = {"packed": (pitch,), "narrow": (4, pitch)}[layout]
+                if not (traj.shape[0] >= steps and tuple(traj.shape[1:]) == row and traj.is_contiguous() and pitch >= n
+                        and traj.dtype == (torch.int32 if layout == "packed" else torch.uint8)):
+                    raise ValueError("finish_episodes: `out` does not have the shape of trajectory_buffers(%d, %r)" % (steps, layout))
+                args.layout, args.traj, args.pitch = _native.LAYOUTS[layout], traj.data_ptr(), pitch
+                result = out
+            t0 = self._t
+            self._t = t0 + steps
+            rc = self._lib.pomdp_finish_episodes(C.byref(args), t0, steps, self._stream())
+            _native.check(rc, "pomdp_finish_episodes")
+        self.done = self._done_bool
+        return result
 
     def _check_driver_use(self, what):
         """The C-side episode loops advance the packed state only: they know nothing of RockSample's side statistics

@@ -71,7 +71,7 @@
 extern "C" {
 #endif
 
-#define POMDP_ABI_VERSION 14
+#define POMDP_ABI_VERSION 15
 
 enum {
     POMDP_E_BADARG = -1,     /* NULL pointer, n < 0, n + lane0 > 2^32 */
@@ -402,6 +402,51 @@ int pomdp_collect_tape_returns(int env, const void *params, uint32_t *state, con
                                const pomdp_return_stats *stats, uint32_t *err, int64_t n, uint64_t seed, uint32_t lane0,
                                uint64_t t0, int64_t k_steps, int flags, void *stream);
 
+/* ---- episodes played to their end (ABI 15) -------------------------------------------------------------------------------
+ * The reference's callers run one episode per env until it ends, then reset that env (rock.py:553-575, tag.py:310-312,
+ * battleship.py:220-222).  A batch does the same without auto-reset: a lane whose episode ended is FROZEN — it keeps its state
+ * and pomdp_<env>_step(flags = 0) returns (ob, reward, done) = (0, 0, 1) for it — until the caller restarts it.
+ *
+ * pomdp_reset_where: the masked reset.  A lane with where[i] != 0 starts the episode pomdp_<env>_reset at the same (seed, lane,
+ * t) gives it (every state word, BattleShip's cached next board included); its ob[i] gets the fresh observation and done[i]
+ * is cleared.  Every other lane keeps its state and done flag and gets ob[i] = -1 (no env observes -1).  ob and done may be
+ * NULL; where == NULL means every lane, and then the results equal pomdp_<env>_reset's.  (env: POMDP_ENV_*, params: its
+ * pomdp_<env>_params, host.) */
+int pomdp_reset_where(int env, const void *params, uint32_t *state, int32_t *ob, uint8_t *done, const uint8_t *where, int64_t n,
+                      uint64_t seed, uint32_t lane0, uint64_t t, void *stream);
+/* pomdp_finish_episodes: the fused loops in frozen mode.  The results are those of k_steps per-step calls: the actions of
+ * pomdp_synthetic_actions at t0 + s (or row s of `tape`, as in pomdp_collect_tape*), then pomdp_<env>_step(flags = 0) at t0 + s.
+ *   - a lane that is live at step s writes its real record; its done flag is set when the episode ends;
+ *   - a lane that is frozen at step s does not step and its state is untouched; its record is action | 1 << 24 (ob 0, reward 0,
+ *     done 1), the action byte being the policy's action at t0 + s (or the tape byte) — what a per-step caller would pass;
+ *   - an out-of-range tape byte of a live lane leaves it untouched, record = the byte (ob, reward, done = 0), and is counted
+ *     in *err; a frozen lane's byte is not counted.
+ * layout POMDP_LAYOUT_PACKED / _NARROW: traj and pitch as in pomdp_collect_layout.  POMDP_LAYOUT_RETURNS: the statistics of
+ * pomdp_collect_returns (same float64 order, Network's float64 reward), booked for live steps only: each adds
+ * ret += disc * reward; disc *= discount; ++steps, and a done step banks ret (ret_done, ret_sum, ++episodes) and restarts at
+ * ret = 0, disc = 1.  With fresh statistics ret_done[i] is lane i's discounted return and steps[i] its length.
+ * `done` (device [n]) is in/out: != 0 = the lane's episode has ended.  lane0 a multiple of 4; any n.  RockSample and
+ * StochasticRock batches that qualify for steps_quad_kernel (n a multiple of 1024, 16-byte-aligned state and statistics, 4-byte-aligned done
+ * and rows, 16 steps per launch or more) take a quad-per-thread loop, everything else one lane per thread; up to
+ * pomdp_fuse_max() steps per launch.  The caller's call counter advances by k_steps.  The existing collection entry points
+ * keep refusing flags = 0. */
+enum { POMDP_LAYOUT_RETURNS = 4 };
+typedef struct pomdp_episode_args {
+    int32_t  env, layout;                /* POMDP_ENV_*; POMDP_LAYOUT_PACKED, _NARROW or _RETURNS */
+    const void *params;                  /* the env's pomdp_<env>_params (host) */
+    uint32_t *state;                     /* device [words][n] */
+    uint8_t  *done;                      /* device [n], in/out: != 0 = the lane's episode has ended; it does not step */
+    const pomdp_tape *tape;              /* NULL = the synthetic policy of pomdp_synthetic_actions at t0 + s */
+    void     *traj;                      /* record layouts: device, as pomdp_collect_layout */
+    int64_t   pitch;
+    const pomdp_return_stats *stats;     /* POMDP_LAYOUT_RETURNS */
+    uint32_t *err;                       /* device uint32, may be NULL */
+    int64_t   n;
+    uint64_t  seed;
+    uint32_t  lane0, reserved;
+} pomdp_episode_args;
+int pomdp_finish_episodes(const pomdp_episode_args *a, uint64_t t0, int64_t k_steps, void *stream);
+
 /* Steps per fused launch of the C-side drivers above (pomdp_rollout_synthetic with POMDP_FUSE_STEPS, pomdp_collect_*,
  * pomdp_heuristic_steps): a launch's fixed cost (kernel start, table build, drain) is paid once per this many steps.
  * pomdp_fuse_max(v) sets it for the calling process (1 <= v <= 256; v <= 0 only reads) and returns the previous value;
@@ -583,7 +628,7 @@ int pomdp_heuristic_steps(int env, const void *params, uint32_t *state, const po
 int         pomdp_abi_version(void);
 const char *pomdp_error_string(int code);
 /* introspection: the kernel (name<template arguments>, as a profiler shows it) that the calling thread's most recent
- * pomdp_rollout_synthetic(POMDP_FUSE_STEPS) / pomdp_collect_synthetic launch picked for the batch geometry it was given;
+ * pomdp_rollout_synthetic(POMDP_FUSE_STEPS) / pomdp_collect_* / pomdp_finish_episodes launch picked for the batch geometry it was given;
  * "" before the first such call.  The string is thread-local and overwritten by the next call. */
 const char *pomdp_last_fused_kernel(void);
 
