@@ -127,14 +127,13 @@ def hipcc_path():
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC"]
 
 
-def build(force=False, verbose=False, defines=(), out=None, jobs=None):
+def build(force=False, verbose=False, out=None, jobs=None):
     """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU): every translation unit of
-    csrc/ to its own object, in parallel, then one link.  `defines` (-DNAME=VALUE strings) and `out` build same-box A/B
-    variants (tools/ab_build.sh)."""
+    csrc/ to its own object, in parallel, then one link.  `out` builds same-box A/B variants (tools/ab_build.sh)."""
     from concurrent.futures import ThreadPoolExecutor
     lib_path = out or INTREE_LIB_PATH
     deps = SOURCES + [HEADER]
-    if (not force and not defines and os.path.exists(lib_path)
+    if (not force and os.path.exists(lib_path)
             and all(os.path.getmtime(lib_path) >= os.path.getmtime(d) for d in deps)):
         return lib_path
     os.makedirs(os.path.dirname(lib_path), exist_ok=True)
@@ -144,7 +143,7 @@ def build(force=False, verbose=False, defines=(), out=None, jobs=None):
 
     def compile_one(unit):
         obj = os.path.join(obj_dir, os.path.splitext(unit)[0] + ".o")
-        cmd = [hipcc] + HIPCC_FLAGS + list(defines) + ["-c", "-o", obj, os.path.join(_PKG, "csrc", unit)]
+        cmd = [hipcc] + HIPCC_FLAGS + ["-c", "-o", obj, os.path.join(_PKG, "csrc", unit)]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)

@@ -159,15 +159,15 @@ __global__ __launch_bounds__(BLOCK) void steps_kernel(uint32_t *__restrict__ sta
     }
     wait_loads();
     const LoopPrio prio(k_steps);
-    constexpr bool POLICY_WITH_STEP = quad_policy && !TAPE && POLICY_WITH_STEP_BLOCKS &&
+    constexpr bool POLICY_WITH_STEP = quad_policy && !TAPE &&
                                       (Env::QUAD_SENSOR || quad_word_env<Env>::value || quad_words_of<Env>::value == 3);
     // The one-lane-per-thread loops with time-shared blocks serve the small shards (2^14 .. 2^18 lanes: one to four waves per
     // SIMD, a step is one wave's dependent chain).  Unrolled by four, a step's picks are register names instead of three
     // selects each and the every-fourth-step branch is straight-line code (UNROLL4).  A lone wave issues an instruction every
     // five to nine cycles whatever it depends on: what counts there is the NUMBER of instructions per step (the next group's
     // blocks drawn in instalments beside the step's own chain, the table entry asked for a step ahead: no gain, docs/HISTORY.md).
-    constexpr bool UNROLL4 = quad_policy && LPT == 1 && (!TAPE || SIMPLE) && STEP_LOOP_UNROLL4;
-    constexpr bool UNROLL4_TAIL = REC && L::ID != LAYOUT_RETURNS && !TAPE && STEP_LOOP_UNROLL4_TAIL;
+    constexpr bool UNROLL4 = quad_policy && LPT == 1 && (!TAPE || SIMPLE);
+    constexpr bool UNROLL4_TAIL = REC && L::ID != LAYOUT_RETURNS && !TAPE;
     // A tape in the unrolled loop is read FOUR rows ahead: row r lives in slot r & 3 (compile-time names: a pending load is never
     // moved or selected); the top of step s asks for row s + 4 into the slot row s left when step s - 1 ended, the end of step s
     // reads row s + 1 — asked for three steps ago, which at a small shard's 0.3 us per step is about the latency of the load.
@@ -380,7 +380,7 @@ __global__ __launch_bounds__(BLOCK) void steps_quad_kernel(uint32_t *__restrict_
     __shared__ typename Env::RecTab tab;
     const uint32_t n_act = (uint32_t)Env::n_actions(p);
     // a quad per thread on a tape: the loop unrolled by two, the tape read two steps ahead (TapeQuadAhead)
-    constexpr bool AHEAD2 = Pol::TAPE && LPT == 4 && TAPE_TWO_STEPS_AHEAD;
+    constexpr bool AHEAD2 = Pol::TAPE && LPT == 4;
     using PolT = typename std::conditional<AHEAD2, TapeQuadAhead, Pol>::type;
     FusedCtx<L, PolT, LPT> cx(action, ob, reward, done, rec, lane0, key0, akey0, n_act, k_steps, tape);
     const uint32_t l0 = cx.l0, glane0 = cx.glane0;           // the thread's first lane within the shard; its global id (a multiple of LPT)
@@ -1301,7 +1301,7 @@ static int launch_steps_fused_l(const typename Env::Params &p, uint32_t *state, 
             if constexpr (quad_policy_of<Finisher<Env, 1, true>>::value) {
                 // full workgroups of an auto-reset batch below the quad gates: the small shards' loops (time-shared blocks, unrolled
                 // by four, RockSample's table-driven step) with the tape read four rows ahead
-                if (!launched && TAPE_SMALL_SHARD_LOOPS && (flags & POMDP_AUTO_RESET) && n % BLOCK == 0) {
+                if (!launched && (flags & POMDP_AUTO_RESET) && n % BLOCK == 0) {
                     bool tab = false;
                     if constexpr (quad_tab<Env>::value && Env::QUAD_SENSOR) tab = k >= 16 && p.num_rocks + 5 <= Env::TAB_ACTIONS;
                     snprintf(variant, sizeof variant, ", 1, true, %s%s", tab ? "true" : "false", lname);
@@ -1325,8 +1325,8 @@ static int launch_steps_fused_l(const typename Env::Params &p, uint32_t *state, 
         return (int)hipGetLastError();
     }
     if constexpr (!std::is_same<L, ColumnsNoAct>::value) {  // the synthetic policy's own forms
-    if constexpr (Env::POOLED_ANY_LPT) {
-        if (!launched && lpt2 && (flags & POMDP_AUTO_RESET) && n % (4 * BLOCK) == 0 && n >= (1 << 20) && Env::WORDS == 1) {
+    if constexpr (Env::POOLED_ANY_LPT && Env::WORDS == 1) {
+        if (!launched && lpt2 && (flags & POMDP_AUTO_RESET) && n % (4 * BLOCK) == 0 && n >= (1 << 20)) {
             POMDP_LAUNCH_STEPS(4, true, qgrid);
             launched = true;
         }

@@ -36,23 +36,52 @@ static inline int grid_for(int64_t n)
     return (int)(b < 1 ? 1 : (b > MAX_BLOCKS ? MAX_BLOCKS : b));
 }
 static inline unsigned blocks_for(int64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
-// below this many lanes one lane per thread is as fast or faster (measured: tools/microbench.hip at 2^16 .. 2^19)
-#ifdef POMDP_LPT2_MIN_LANES                                   // same-box A/B builds (tools/ab_build.sh)
-constexpr int64_t LPT2_MIN_LANES = POMDP_LPT2_MIN_LANES;
-#else
-constexpr int64_t LPT2_MIN_LANES = 1 << 18;
-#endif
-#ifdef POMDP_STEP_QUAD_MIN_LANES                              // same-box A/B builds (tools/ab_build.sh)
-constexpr int64_t STEP_QUAD_MIN_LANES = POMDP_STEP_QUAD_MIN_LANES;
-#else
-constexpr int64_t STEP_QUAD_MIN_LANES = 1 << 19;
-#endif
 
-#ifdef POMDP_STEP_TILES                                       // same-box A/B builds (tools/ab_build.sh): tiles per thread of the one-step quad kernels
-constexpr int STEP_TILES = POMDP_STEP_TILES;
-#else
-constexpr int STEP_TILES = 1;                                 // measured (round 6): two tiles per thread 7.6 against 6.5 us per call — DESIGN.md §5.2
-#endif
+// ---- the gates: the batch sizes at which the launchers change loops
+// below this many lanes one lane per thread is as fast or faster (measured: tools/microbench.hip at 2^16 .. 2^19)
+constexpr int64_t LPT2_MIN_LANES = 1 << 18;
+constexpr int64_t STEP_QUAD_MIN_LANES = 1 << 19;
+// the priority ladder (LoopPrio) only where a SIMD holds two or more of the launch's waves (256-thread workgroups: from two per
+// CU; measured at 2^17 lanes with one lane per thread and at 2^19 with a quad: 3-8 % either way)
+constexpr unsigned PRIO_MIN_WGS = 2 * 256;
+// Smallest batch each quad-per-thread loop takes (1024 lanes per workgroup).  Measured on MI355X, us per fused step at
+// 2^17 / 2^18 / 2^19 / 2^20 lanes (profiles/r02_small_shards_gates.txt, r02k_small_shards.txt): RockSample(7,8) quad 1.50 /
+// 1.52 / 1.82 / 2.89 against 1.25 / 1.39 / 1.99 with one or two lanes per thread; Tag (table-driven) 1.59 / 1.61 / 1.83 /
+// 2.67 against 0.96 / 1.43 / 2.00; Tiger 0.67 / 0.67 / 1.21 / 2.51 against 0.44 / 0.85 / 1.41 / 2.66; Network 2.30 / 2.30 / 2.91 /
+// 4.72 against 1.45 / 1.94 / 3.32 / 5.99 — below these sizes every kernel is bound by the latency of one wave's step
+// (1.1-2.3 us), and more, lighter waves hide it better than fewer, heavier ones.
+// Re-measured at the end of round 3 (priority ladder, RockSample's auto-reset from the sensor block; profiles/
+// r03b_gates.txt): RockSample between 2^19 and 3 * 2^18 lanes is faster with the pooled two-lanes-per-thread loop (four waves
+// per SIMD instead of two or two and a half; (15,15) at 2^19 lanes 1.25 against 1.46 us per step, (7,8) at 5 * 2^17 lanes
+// 1.50 against 1.65) and from 3 * 2^18 lanes — three workgroups per CU — with the quad loop; Tiger at 2^18 lanes with one
+// lane per thread (0.66 against 0.72).  StochasticRock has no pooled loop and keeps 2^19.
+// Round 4: BattleShip's quad loop from 2^16 lanes (feed2 halved what its board pool costs, the one-lane loop builds boards on
+// the spot with the wave-cooperative builder: 2^16 / 2^17 lanes 0.995 / 1.036 against 1.074 / 1.209 us per step).
+// Round 5 (ABI 13: Tiger's and Tag's steps read one word of the quad's STEP block): the one-lane loops time-share that block
+// like the policy's, the quad loops have it thread-local — Tiger 2^18 / 2^19 lanes 0.382 / 0.811 us per step with one lane
+// per thread against 0.522 / 0.650 with a quad, Tag 2^18 0.765 against 0.919 (2^19: the pooled two-lane loop 1.74, the quad
+// loop 1.08): the gates stay.
+constexpr int64_t QUAD_MIN_ROCK = 3 << 18, QUAD_MIN_STOCHROCK = 1 << 19, QUAD_MIN_TAG = 1 << 19, QUAD_MIN_GENERIC = 1 << 19,
+                  QUAD_MIN_NETWORK = 1 << 19, QUAD_MIN_BATTLESHIP = 1 << 16;
+
+// BattleShip with half a quad per thread (battleship_steps_quad_kernel<.., 2>): the shards the quad loop gives two waves per
+// SIMD or fewer.
+constexpr int64_t BS_PAIR_MIN_LANES = 1 << 17, BS_PAIR_MAX_LANES = 1 << 19;
+constexpr int64_t BS_VIS_LDS_MAX_LANES = 1 << 19;                // the visited mask in LDS up to this many lanes (48 B of LDS per lane)
+// RockSample / StochasticRock with half a quad per thread (steps_quad_kernel<.., 2>), records and typed planes only.  Measured
+// against both neighbours (profiles/r06_rock_pair_ab.txt, us per step, Packed): RockSample(7,8) at 3 * 2^17 lanes level with
+// the pooled kernel (0.80 / 0.81), 13 * 2^15 .. 5 * 2^17 ahead (2^19: 1.07 -> 0.87), at 3 * 2^18 level with the quad loop;
+// StochasticRock ahead of the pooled kernel from 3 * 2^17 (1.47 -> 1.11; 7 * 2^16: 2.06 -> 1.35) and behind the quad loop from
+// 2^19 (1.32 / 1.36).  The returns sink loses at 2^19 (1.01 / 1.05: its float64 chain wants the quad's four independent
+// lanes) and is not built in this form.
+constexpr int64_t ROCK_PAIR_MAX_LANES = (3 << 18) - 1, STOCHROCK_PAIR_MAX_LANES = (1 << 19) - 1;
+constexpr int64_t ROCK_PAIR_MIN_LANES = (3 << 17) + 1, STOCHROCK_PAIR_MIN_LANES = 3 << 17;
+// Tag (one opponent, table-driven) the same way (tag_steps_quad_kernel<.., 2>), every pair sink: ahead of the one-lane-per-thread
+// loop from 3 * 2^17 lanes (0.91 -> 0.80 us per step of records; 7 * 2^16: 1.21 -> 0.92; 2^19, against the quad loop: 1.08 ->
+// 0.92; returns 1.18 -> 1.03), level with the quad loop at 3 * 2^18 (profiles/r06_tag_pair_ab.txt).  Tiger's loop in this form
+// is level with its quad loop at 2^19 (0.63) and behind below: not built.
+constexpr int64_t TAG_PAIR_MAX_LANES = (3 << 18) - 1;
+constexpr int64_t TAG_PAIR_MIN_LANES = 3 << 17;
 
 // envs whose lanes carry the board of their next episode (BattleShip): `next` is loaded only where a lane may need it
 template <class Env, class = void> struct has_next : std::false_type {};
@@ -324,22 +353,14 @@ static __device__ __forceinline__ void wait_loads() { __builtin_amdgcn_s_waitcnt
 // slots the others leave) until the others are as close to the end, and a SIMD's waves finish within a step or two of
 // each other: RockSample 159 -> 141 us per 64-step launch, 59 -> 54 per 20-step launch (thresholds measured at k = 16 ..
 // 64: the geometric ladder beats quartiles, and it scales with k).
-#ifndef POMDP_PRIO_MIN_WGS                                     // same-box A/B builds (tools/ab_build.sh)
-#define POMDP_PRIO_MIN_WGS (2 * 256)
-#endif
 struct LoopPrio {
     int k, t0, t1, t2;
     bool on;
-    // Only where a SIMD holds two or more of the launch's waves (256-thread workgroups: from two per CU; measured at 2^17
-    // lanes with one lane per thread and at 2^19 with a quad: 3-8 % either way); a lone wave has nobody to yield to.
+    // Only from PRIO_MIN_WGS workgroups: a lone wave has nobody to yield to.
     __device__ __forceinline__ explicit LoopPrio(int k_steps, bool enable = true)
         : k(k_steps), t0(k_steps >> 4 > 0 ? k_steps >> 4 : 1), t1((3 * k_steps) >> 4), t2((7 * k_steps) >> 4)
     {
-#ifdef POMDP_NO_LOOP_PRIO                                     // same-box A/B builds (tools/ab_build.sh)
-        on = false;
-#else
-        on = enable && gridDim.x >= (unsigned)POMDP_PRIO_MIN_WGS;
-#endif
+        on = enable && gridDim.x >= PRIO_MIN_WGS;
     }
     // The step loop runs as four consecutive segments, one per priority: segment `seg` sets its priority and returns the
     // step at which it ends (`unit`: the loop's stride — the heuristic loop advances four steps at a time).  The ladder
@@ -396,105 +417,6 @@ static inline bool bad_range(int64_t n, uint32_t lane0) { return n < 0 || (uint6
 // the launcher that takes it sets the pointer back to null (defined in api.hip)
 extern thread_local uint32_t *tl_host_flag;
 extern thread_local uint32_t tl_flag_value;
-
-// Smallest batch each quad-per-thread loop takes (1024 lanes per workgroup).  Measured on MI355X, us per fused step at
-// 2^17 / 2^18 / 2^19 / 2^20 lanes (profiles/r02_small_shards_gates.txt, r02k_small_shards.txt): RockSample(7,8) quad 1.50 /
-// 1.52 / 1.82 / 2.89 against 1.25 / 1.39 / 1.99 with one or two lanes per thread; Tag (table-driven) 1.59 / 1.61 / 1.83 /
-// 2.67 against 0.96 / 1.43 / 2.00; Tiger 0.67 / 0.67 / 1.21 / 2.51 against 0.44 / 0.85 / 1.41 / 2.66; Network 2.30 / 2.30 / 2.91 /
-// 4.72 against 1.45 / 1.94 / 3.32 / 5.99 — below these sizes every kernel is bound by the latency of one wave's step
-// (1.1-2.3 us), and more, lighter waves hide it better than fewer, heavier ones.
-// Re-measured at the end of round 3 (priority ladder, RockSample's auto-reset from the sensor block; profiles/
-// r03b_gates.txt): RockSample between 2^19 and 3 * 2^18 lanes is faster with the pooled two-lanes-per-thread loop (four waves
-// per SIMD instead of two or two and a half; (15,15) at 2^19 lanes 1.25 against 1.46 us per step, (7,8) at 5 * 2^17 lanes
-// 1.50 against 1.65) and from 3 * 2^18 lanes — three workgroups per CU — with the quad loop; Tiger at 2^18 lanes with one
-// lane per thread (0.66 against 0.72).  StochasticRock has no pooled loop and keeps 2^19.
-// Round 4: BattleShip's quad loop from 2^16 lanes (feed2 halved what its board pool costs, the one-lane loop builds boards on
-// the spot with the wave-cooperative builder: 2^16 / 2^17 lanes 0.995 / 1.036 against 1.074 / 1.209 us per step).
-// Round 5 (ABI 13: Tiger's and Tag's steps read one word of the quad's STEP block): the one-lane loops time-share that block
-// like the policy's, the quad loops have it thread-local — Tiger 2^18 / 2^19 lanes 0.382 / 0.811 us per step with one lane
-// per thread against 0.522 / 0.650 with a quad, Tag 2^18 0.765 against 0.919 (2^19: the pooled two-lane loop 1.74, the quad
-// loop 1.08): the gates stay.
-// POMDP_QUAD_MIN_LANES overrides all of them at build time for same-box A/B runs (tools/ab_build.sh lib ... -D...).
-#ifdef POMDP_QUAD_MIN_LANES
-constexpr int64_t QUAD_MIN_ROCK = POMDP_QUAD_MIN_LANES, QUAD_MIN_STOCHROCK = POMDP_QUAD_MIN_LANES, QUAD_MIN_TAG = POMDP_QUAD_MIN_LANES,
-                  QUAD_MIN_GENERIC = POMDP_QUAD_MIN_LANES, QUAD_MIN_NETWORK = POMDP_QUAD_MIN_LANES, QUAD_MIN_BATTLESHIP = POMDP_QUAD_MIN_LANES;
-#else
-constexpr int64_t QUAD_MIN_ROCK = 3 << 18, QUAD_MIN_STOCHROCK = 1 << 19, QUAD_MIN_TAG = 1 << 19, QUAD_MIN_GENERIC = 1 << 19,
-                  QUAD_MIN_NETWORK = 1 << 19, QUAD_MIN_BATTLESHIP = 1 << 16;
-#endif
-
-// BattleShip with half a quad per thread (battleship_steps_quad_kernel<.., 2>): the shards the quad loop gives two waves per
-// SIMD or fewer.  -DPOMDP_BS_PAIR_MAX_LANES=0 builds the A arm (quad loop everywhere).
-#ifdef POMDP_BS_PAIR_MAX_LANES
-constexpr int64_t BS_PAIR_MAX_LANES = POMDP_BS_PAIR_MAX_LANES;
-#else
-constexpr int64_t BS_PAIR_MAX_LANES = 1 << 19;
-#endif
-// RockSample / StochasticRock with half a quad per thread (steps_quad_kernel<.., 2>), records and typed planes only.  Measured
-// against both neighbours (profiles/r06_rock_pair_ab.txt, us per step, Packed): RockSample(7,8) at 3 * 2^17 lanes level with
-// the pooled kernel (0.80 / 0.81), 13 * 2^15 .. 5 * 2^17 ahead (2^19: 1.07 -> 0.87), at 3 * 2^18 level with the quad loop;
-// StochasticRock ahead of the pooled kernel from 3 * 2^17 (1.47 -> 1.11; 7 * 2^16: 2.06 -> 1.35) and behind the quad loop from
-// 2^19 (1.32 / 1.36).  The returns sink loses at 2^19 (1.01 / 1.05: its float64 chain wants the quad's four independent
-// lanes) and is not built in this form.  -DPOMDP_ROCK_PAIR_MAX_LANES=0: the A arm; with _MIN_LANES: one gate for both envs.
-#ifdef POMDP_ROCK_PAIR_MAX_LANES
-constexpr int64_t ROCK_PAIR_MAX_LANES = POMDP_ROCK_PAIR_MAX_LANES, STOCHROCK_PAIR_MAX_LANES = POMDP_ROCK_PAIR_MAX_LANES;
-#else
-constexpr int64_t ROCK_PAIR_MAX_LANES = (3 << 18) - 1, STOCHROCK_PAIR_MAX_LANES = (1 << 19) - 1;
-#endif
-#ifdef POMDP_ROCK_PAIR_MIN_LANES
-constexpr int64_t ROCK_PAIR_MIN_LANES = POMDP_ROCK_PAIR_MIN_LANES, STOCHROCK_PAIR_MIN_LANES = POMDP_ROCK_PAIR_MIN_LANES;
-#else
-constexpr int64_t ROCK_PAIR_MIN_LANES = (3 << 17) + 1, STOCHROCK_PAIR_MIN_LANES = 3 << 17;
-#endif
-#ifdef POMDP_NO_STEP_LOOP_UNROLL4                              // the A arm: the time-shared one-lane-per-thread loops step by step
-constexpr bool STEP_LOOP_UNROLL4 = false;
-#else
-constexpr bool STEP_LOOP_UNROLL4 = true;
-#endif
-#ifdef POMDP_NO_STEP_LOOP_UNROLL4_TAIL                         // the A arm: every step of a group of four behind its own bound check
-constexpr bool STEP_LOOP_UNROLL4_TAIL = false;
-#else
-constexpr bool STEP_LOOP_UNROLL4_TAIL = true;
-#endif
-#ifdef POMDP_NO_TAPE_TWO_STEPS_AHEAD                           // the A arm: the tape's row of step s + 1 asked for at the top of step s
-constexpr bool TAPE_TWO_STEPS_AHEAD = false;
-#else
-constexpr bool TAPE_TWO_STEPS_AHEAD = true;
-#endif
-#ifdef POMDP_NO_TAPE_SMALL_SHARD_LOOPS                         // the A arm: a tape below the quad gates always takes the general loop
-constexpr bool TAPE_SMALL_SHARD_LOOPS = false;
-#else
-constexpr bool TAPE_SMALL_SHARD_LOOPS = true;
-#endif
-#ifdef POMDP_POLICY_AFTER_STEP                                 // the A arm: the policy's block drawn after the lane step (until round 6)
-constexpr bool POLICY_WITH_STEP_BLOCKS = false;
-#else
-constexpr bool POLICY_WITH_STEP_BLOCKS = true;
-#endif
-// Tag (one opponent, table-driven) the same way (tag_steps_quad_kernel<.., 2>), every pair sink: ahead of the one-lane-per-thread
-// loop from 3 * 2^17 lanes (0.91 -> 0.80 us per step of records; 7 * 2^16: 1.21 -> 0.92; 2^19, against the quad loop: 1.08 ->
-// 0.92; returns 1.18 -> 1.03), level with the quad loop at 3 * 2^18 (profiles/r06_tag_pair_ab.txt).  Tiger's loop in this form
-// is level with its quad loop at 2^19 (0.63) and behind below: not built.
-#ifdef POMDP_TAG_PAIR_MAX_LANES
-constexpr int64_t TAG_PAIR_MAX_LANES = POMDP_TAG_PAIR_MAX_LANES;
-#else
-constexpr int64_t TAG_PAIR_MAX_LANES = (3 << 18) - 1;
-#endif
-#ifdef POMDP_TAG_PAIR_MIN_LANES
-constexpr int64_t TAG_PAIR_MIN_LANES = POMDP_TAG_PAIR_MIN_LANES;
-#else
-constexpr int64_t TAG_PAIR_MIN_LANES = 3 << 17;
-#endif
-#ifdef POMDP_BS_VIS_LDS_MAX_LANES                             // the visited mask in LDS up to this many lanes (48 B of LDS per lane)
-constexpr int64_t BS_VIS_LDS_MAX_LANES = POMDP_BS_VIS_LDS_MAX_LANES;
-#else
-constexpr int64_t BS_VIS_LDS_MAX_LANES = 1 << 19;
-#endif
-#ifdef POMDP_BS_PAIR_MIN_LANES
-constexpr int64_t BS_PAIR_MIN_LANES = POMDP_BS_PAIR_MIN_LANES;
-#else
-constexpr int64_t BS_PAIR_MIN_LANES = 1 << 17;
-#endif
 
 // steps per fused launch of the C-side drivers (pomdp_fuse_max; defined in api.hip).  One place instead of a constant per
 // driver; a launch's fixed cost is paid once per this many steps, results never depend on it
@@ -574,10 +496,8 @@ using BattleShip4 = BattleShipEnv<4>;
 #define POMDP_EACH_ENV(M, X)                                                                                                  \
     M(X, Rock1) M(X, Rock2) M(X, StochRock1) M(X, StochRock2) M(X, TagEnv) M(X, BattleShip1) M(X, BattleShip2)                  \
     M(X, BattleShip3) M(X, BattleShip4) M(X, TigerEnv) M(X, NetworkEnv)
-#ifndef POMDP_NO_EXTERN_LAUNCHERS
 POMDP_EACH_ENV(POMDP_STEP_LAUNCHERS, extern)
 POMDP_EACH_ENV(POMDP_FUSED_LAUNCHER, extern)
-#endif
 
 } // namespace pomdp
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Fused-launch time per step at the shard sizes a 2^20-lane batch leaves per GPU (2^17 .. 2^20, and below), for every
 library variant given: python tools/gpu_small_shards.py [libA.so libB.so ...]   (default: the product library).
-Variants come from tools/ab_build.sh (e.g. -DPOMDP_QUAD_MIN_LANES=4096: the quad-per-thread loops from 4096 lanes up).
+Variants come from tools/ab_build.sh rev (e.g. a worktree with QUAD_MIN_ROCK = 4096: the quad-per-thread loop from 4096 lanes up).
 Prints us per step of collect_synthetic($SHARD_K or 256, layout=$SHARD_LAYOUT or "packed"; "returns": collect_returns) by HIP
 events, and the kernel the launcher picked.  SHARD_TAPE=1: the same launches on a tape of the caller's actions (collect_tape)."""
 import os

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Registers / occupancy / LDS of every kernel in the product library, from hipcc's -Rpass-analysis=kernel-resource-usage
-(dev aid; cross-compiles without a GPU).  usage: python tools/kernel_resources.py [filter substring] [-D...]"""
+(dev aid; cross-compiles without a GPU).  usage: python tools/kernel_resources.py [filter substring ...]"""
 import os
 import re
 import subprocess
@@ -12,18 +12,18 @@ from gym_pomdp_amd import _native  # noqa: E402
 from concurrent.futures import ThreadPoolExecutor  # noqa: E402
 
 
-def remarks(unit, defs=()):
+def remarks(unit):
     cmd = ["/opt/rocm/bin/hipcc"] + _native.HIPCC_FLAGS + ["-c", "-o", "/dev/null", os.path.join(REPO, "gym_pomdp_amd/csrc", unit),
-                                                          "-Rpass-analysis=kernel-resource-usage"] + list(defs)
+                                                          "-Rpass-analysis=kernel-resource-usage"]
     return subprocess.run(cmd, capture_output=True, text=True).stderr
 
 
-def collect(defs=(), units=None):
+def collect(units=None):
     """-> [{"kernel": demangled name without arguments, "vgpr", "sgpr", "occupancy", "lds", "scratch"}] for every kernel of the
     translation units (default: all of the product library's)"""
     units = list(units or _native.UNITS)
     with ThreadPoolExecutor(max_workers=len(units)) as ex:
-        out = "\n".join(ex.map(lambda u: remarks(u, defs), units))
+        out = "\n".join(ex.map(remarks, units))
     cur, rows = None, []
     for line in out.splitlines():
         m = re.search(r"remark: +(.*?) \[-Rpass", line)
@@ -47,10 +47,9 @@ def collect(defs=(), units=None):
 
 
 if __name__ == "__main__":
-    flt = [a for a in sys.argv[1:] if not a.startswith("-D")]
-    defs = [a for a in sys.argv[1:] if a.startswith("-D")]
+    flt = sys.argv[1:]
     print("%-5s %-5s %-4s %-7s %-7s %s" % ("VGPR", "SGPR", "occ", "LDS", "scratch", "kernel"))
-    for r in collect(defs):
+    for r in collect():
         if flt and not all(f in r["kernel"] for f in flt):
             continue
         print("%-5s %-5s %-4s %-7s %-7s %s" % (r["vgpr"], r["sgpr"], r["occupancy"], r["lds"], r["scratch"], r["kernel"][:150]))
