@@ -464,30 +464,45 @@ struct RockEnv {
     //           (StochasticRock: 6);
     //   a >= 5: bits 0-27 = the sensor threshold's high bits (thr >> 26 <= 2^27: a sensor that is always right at distance 0
     //           has thr = 2^53) at this distance; fallback 6 — the kernel compares against (H >> 5) | 6 << 28 (one
-    //           v_alignbit_b32), so the threshold test and the tie test read the entry as it is.
+    //           v_alignbit_b32), so the threshold test and the tie test read the entry as it is;
+    //   a <  5: bit 27 set.  (H >> 5) | 6 << 28 has bit 27 clear, so only a CHECK's entry can tie with it: the tie test needs
+    //           no test of the action.
     // Outcome codes: 0 = bad rock sampled (-10), 1 = penalty (-100, done), 2 = good rock sampled (+10), 3 = east exit (+10,
     // done), 6 = nothing (0) — a sampled rock's own code IS its outcome code, done is bit 0, and the reward byte is one
     // v_perm_b32 lookup in an 8-byte constant.
+    // One state word (K <= 12): the entry is 8 bytes, read with one ds_read_b64 (17 x 256 x 8 = 34 KB of LDS per workgroup,
+    // four workgroups per CU fit).  The second word holds what the first leaves to tests of the action:
+    //   bits 16-23 = a move's position delta (the first word's low byte; 0 in every other entry, so it is XORed in unselected);
+    //   a >= 5: bits 0-4 = the bit offset 2 a - 1 of the CHECKed rock's upper code bit ("good"), bits 8-9 = 3; every other
+    //           entry 0 — the observation is (bits 8-9) & (2 << 8 if the reading matches the rock, else 1 << 8), zero unless
+    //           a CHECK.
+    // Two state words keep 4-byte entries (21 x 256 x 8 = 42 KB would leave three workgroups per CU) and test the action.
     static constexpr uint32_t REC_LUT_LO = 0x0A0A9CF6u, REC_LUT_HI = 0x00000000u;   // reward byte by outcome code 0..7
-    struct RecTab { uint32_t e[TAB_ACTIONS][256]; };
+    using TabEntry = typename std::conditional<W == 1, uint2, uint32_t>::type;
+    struct RecTab { TabEntry e[TAB_ACTIONS][256]; };
     static __device__ __forceinline__ void build_rec_tab(RecTab &tab, const Shared &sh, const Params &p, int pos)
     {
         const uint32_t x = (uint32_t)pos & 15u, y = (uint32_t)pos >> 4, size = (uint32_t)p.size, K = (uint32_t)p.num_rocks;
         const int id = sh.grid[x * 16 + y];
         const uint32_t NOTHING = 6u << 28, PENALTY = (STOCH ? 6u : 1u) << 28, EXIT_EAST = 3u << 28;
+        const uint32_t NO_TIE = 1u << 27;
         for (int a = 0; a < 5 + (int)K && a < TAB_ACTIONS; ++a) {
-            uint32_t e;
+            uint32_t e, f = 0u;
             if (a < 4) {
                 const uint32_t nx = x + (uint32_t)((a == 1) - (a == 3)), ny = y + (uint32_t)((a == 0) - (a == 2));
                 const bool inside = max(nx, ny) < size;
                 e = inside ? (((uint32_t)pos ^ (nx | (ny << 4))) | NOTHING) : (a == 1 ? EXIT_EAST : PENALTY);
+                e |= NO_TIE;
+                f = (e & 0xFFu) << 16;
             } else if (a == 4) {
                 const bool rock = (uint32_t)id < K;
-                e = (rock ? ((8u + 2u * (uint32_t)id) | 0x80000000u) : 0u) | PENALTY;
+                e = (rock ? ((8u + 2u * (uint32_t)id) | 0x80000000u) : 0u) | PENALTY | NO_TIE;
             } else {
                 e = sh.thr[__builtin_amdgcn_sad_u8(x | (y << 8), sh.rpos[a - 5], 0u) & 31u].x | NOTHING;
+                f = (2u * (uint32_t)a - 1u) | (3u << 8);
             }
-            tab.e[a][pos] = e;
+            if constexpr (W == 1) tab.e[a][pos] = make_uint2(e, f);
+            else tab.e[a][pos] = e;
         }
     }
     // rock.py:123-194 for one lane: s -> s' (the fresh episode `fresh` if the step ends this one), rec = the step's record.
@@ -499,29 +514,50 @@ struct RockEnv {
                                                     uint32_t &rec, LowWord lo)
     {
         const uint32_t s_lo = (uint32_t)s, s_hi = W == 2 ? (uint32_t)((uint64_t)s >> 32) : 0u;
-        const uint32_t e = tab.e[a][s_lo & 0xFFu];
-        // SAMPLE (rock.py:160-169): the cell's rock code, read at the entry's offset (entries of the other classes: the
-        // sign bit is clear, so whatever this reads is never used)
-        const bool up_s = W == 2 && (e & 32u) != 0u;                            // the code lies in the upper word
-        const uint32_t code = __builtin_amdgcn_ubfe(up_s ? s_hi : s_lo, e, 2u);
-        const bool ok = ((int32_t)e < 0) & (code != 1u);                        // an uncollected rock with an id < K is underfoot
-        const uint32_t collect = (code ^ 1u) << (e & 31u);                      // its code -> 1
-        // moves (rock.py:134-158): the position delta, for that class only
-        const uint32_t move = (a < 4u ? e : 0u) & 0xFFu;
-        const uint32_t d_lo = (ok & !up_s) ? collect : move, d_hi = (ok & up_s) ? collect : 0u;
-        const uint32_t oc = ok ? code : __builtin_amdgcn_ubfe(e, 28u, 3u);      // outcome code
-        const uint32_t rbyte = __builtin_amdgcn_perm(REC_LUT_HI, REC_LUT_LO, (oc << 16) | 0x0C000C0Cu);   // reward byte << 16
-        const uint32_t done = oc & 1u;
-        // CHECK rock a - 5 (rock.py:171-175, 401-407): its code sits at bits 2a-2, 2a-1 of the state; good = the upper one
-        const uint32_t gi = 2u * a - 1u;
-        const bool good = __builtin_amdgcn_ubfe((W == 2 && (gi & 32u)) ? s_hi : s_lo, gi, 1u) != 0u;
-        const uint32_t kh = __builtin_amdgcn_alignbit(12u, H, 5u);              // (H >> 5) | 6 << 28: compares with the entry itself
-        bool correct = kh < e;
-        if (a > 4u && kh == e) correct = (lo() >> 6) <= thr_lo_of(sh, State{s}, (int)a - 5);   // probability 2^-27
-        const uint32_t ob = a > 4u ? ((good == correct) ? 2u << 8 : 1u << 8) : 0u;
-        rec = rbyte | (done << 24) | ob | a;
-        if constexpr (W == 2) s = done ? fresh : (S)(((uint64_t)(s_hi ^ d_hi) << 32) | (s_lo ^ d_lo));
-        else s = done ? fresh : (S)(s_lo ^ d_lo);
+        if constexpr (W == 1) {
+            const uint2 ef = tab.e[a][s_lo & 0xFFu];
+            const uint32_t e = ef.x, f = ef.y;
+            // SAMPLE (rock.py:160-169): the cell's rock code, read at the entry's offset (entries of the other classes: the
+            // sign bit is clear, so whatever this reads is never used)
+            const uint32_t code = __builtin_amdgcn_ubfe(s_lo, e, 2u);
+            const bool ok = ((int32_t)e < 0) & (code != 1u);                    // an uncollected rock with an id < K is underfoot
+            const uint32_t collect = (code ^ 1u) << (e & 31u);                  // its code -> 1
+            const uint32_t d = ok ? collect : __builtin_amdgcn_ubfe(f, 16u, 8u); // ... or a move's position delta (0 for the rest)
+            const uint32_t oc = ok ? code : __builtin_amdgcn_ubfe(e, 28u, 3u);  // outcome code
+            const uint32_t rbyte = __builtin_amdgcn_perm(REC_LUT_HI, REC_LUT_LO, (oc << 16) | 0x0C000C0Cu);   // reward byte << 16
+            const uint32_t done = oc & 1u;
+            // CHECK rock a - 5 (rock.py:171-175, 401-407): good = its upper code bit, at the entry's offset 2a-1
+            const bool good = __builtin_amdgcn_ubfe(s_lo, f, 1u) != 0u;
+            const uint32_t kh = __builtin_amdgcn_alignbit(12u, H, 5u);          // (H >> 5) | 6 << 28: compares with the entry itself
+            bool correct = kh < e;
+            if (kh == e) correct = (lo() >> 6) <= thr_lo_of(sh, State{s}, (int)a - 5);   // a CHECK only (NO_TIE); probability 2^-27
+            const uint32_t ob = f & ((good == correct) ? 2u << 8 : 1u << 8);    // 0 unless a CHECK
+            rec = rbyte | (done << 24) | ob | a;
+            s = done ? fresh : (S)(s_lo ^ d);
+        } else {
+            const uint32_t e = tab.e[a][s_lo & 0xFFu];
+            // SAMPLE (rock.py:160-169): the cell's rock code, read at the entry's offset (entries of the other classes: the
+            // sign bit is clear, so whatever this reads is never used)
+            const bool up_s = (e & 32u) != 0u;                                      // the code lies in the upper word
+            const uint32_t code = __builtin_amdgcn_ubfe(up_s ? s_hi : s_lo, e, 2u);
+            const bool ok = ((int32_t)e < 0) & (code != 1u);                        // an uncollected rock with an id < K is underfoot
+            const uint32_t collect = (code ^ 1u) << (e & 31u);                      // its code -> 1
+            // moves (rock.py:134-158): the position delta, for that class only
+            const uint32_t move = (a < 4u ? e : 0u) & 0xFFu;
+            const uint32_t d_lo = (ok & !up_s) ? collect : move, d_hi = (ok & up_s) ? collect : 0u;
+            const uint32_t oc = ok ? code : __builtin_amdgcn_ubfe(e, 28u, 3u);      // outcome code
+            const uint32_t rbyte = __builtin_amdgcn_perm(REC_LUT_HI, REC_LUT_LO, (oc << 16) | 0x0C000C0Cu);   // reward byte << 16
+            const uint32_t done = oc & 1u;
+            // CHECK rock a - 5 (rock.py:171-175, 401-407): its code sits at bits 2a-2, 2a-1 of the state; good = the upper one
+            const uint32_t gi = 2u * a - 1u;
+            const bool good = __builtin_amdgcn_ubfe((gi & 32u) ? s_hi : s_lo, gi, 1u) != 0u;
+            const uint32_t kh = __builtin_amdgcn_alignbit(12u, H, 5u);              // (H >> 5) | 6 << 28: compares with the entry itself
+            bool correct = kh < e;
+            if (a > 4u && kh == e) correct = (lo() >> 6) <= thr_lo_of(sh, State{s}, (int)a - 5);   // probability 2^-27
+            const uint32_t ob = a > 4u ? ((good == correct) ? 2u << 8 : 1u << 8) : 0u;
+            rec = rbyte | (done << 24) | ob | a;
+            s = done ? fresh : (S)(((uint64_t)(s_hi ^ d_hi) << 32) | (s_lo ^ d_lo));
+        }
     }
 
     // observation of a CHECK from the sensor's high word (rock.py:404-407); `lo` yields the low word on a tie

@@ -414,15 +414,18 @@ __global__ __launch_bounds__(BLOCK) void steps_quad_kernel(uint32_t *__restrict_
     const int K = p.num_rocks;
     const uint32_t start = (uint32_t)p.start_x | ((uint32_t)p.start_y << 4);
     const LoopPrio prio(k_steps);
+    constexpr uint32_t SENSOR_BLOCK = Env::SENSOR_BLOCK;
+    // a quad per thread: the quad's STEP blocks have counter words 0 and 3 fixed for the launch (philox4x32_10_fixed)
+    const PhiloxFixed sensor_fx = philox_fixed(glane0 >> 2, ((uint32_t)POMDP_STREAM_STEP << 24) | SENSOR_BLOCK, key0.k1);
+    const PhiloxFixed gate_fx = philox_fixed(glane0 >> 2, (uint32_t)POMDP_STREAM_STEP << 24, key0.k1);
     auto step_body = [&](const int s, const auto par_) __attribute__((always_inline)) {
         constexpr int PAR = decltype(par_)::value;           // AHEAD2: s & 1
         const RngKey key = cx.key(key0, s);
         // the quad's sensor words of this step (StochasticRock: block 2 of the stream — block 0 gates the actions, rock.py:443)
         // — the words its fresh episodes start from as well — and the actions of the next call counter
-        constexpr uint32_t SENSOR_BLOCK = Env::SENSOR_BLOCK;
         uint32_t H[LPT], G[LPT];
         if constexpr (LPT == 4) {
-            const uint4 sw = philox4x32_10(glane0 >> 2, key.t_lo, key.t_hi, ((uint32_t)POMDP_STREAM_STEP << 24) | SENSOR_BLOCK, key.k0, key.k1);
+            const uint4 sw = philox4x32_10_fixed(sensor_fx, key.t_lo, key.t_hi, key.k0, key.k1);
             H[0] = sw.x; H[1] = sw.y; H[2] = sw.z; H[3] = sw.w;
         } else {
             pair_shared(s, e0 != 0u, [&](int sb) { return Env::quad_block(cx.key(key0, sb), glane0, SENSOR_BLOCK); }, H, sp0, sp1);
@@ -436,7 +439,7 @@ __global__ __launch_bounds__(BLOCK) void steps_quad_kernel(uint32_t *__restrict_
         for (int j = 0; j < LPT; ++j) acts[j] = true;
         if constexpr (Env::STOCHASTIC) {                                       // the action is applied iff binomial(1, p_move) says so
             if constexpr (LPT == 4) {
-                const uint4 gw = Env::quad_block(key, glane0, 0u);
+                const uint4 gw = philox4x32_10_fixed(gate_fx, key.t_lo, key.t_hi, key.k0, key.k1);
                 G[0] = gw.x; G[1] = gw.y; G[2] = gw.z; G[3] = gw.w;
             } else {
                 pair_shared(s, e0 != 0u, [&](int sb) { return Env::quad_block(cx.key(key0, sb), glane0, 0u); }, G, gp0, gp1);
@@ -461,7 +464,7 @@ __global__ __launch_bounds__(BLOCK) void steps_quad_kernel(uint32_t *__restrict_
             // a tape may hold anything: an out-of-range action leaves the lane untouched, (ob, reward, done) = (0, 0, 0), and is counted
             const bool valid = !Pol::TAPE || a_taken[j] < n_act;
             Env::step_rec(sh, tab, sj, valid ? a_taken[j] : 0u, H[j], (S)((uint64_t)start | ((uint64_t)codes[j] << 8)), rec[j],
-                          [&]() { return Env::elem(Env::quad_block(key, lane, SENSOR_BLOCK + 1u), e0 + (uint32_t)j); });
+                          [&]() { return Env::elem(Env::quad_block(rare_key(key), lane, SENSOR_BLOCK + 1u), e0 + (uint32_t)j); });
             if constexpr (Env::STOCHASTIC) {                                // the gate said no (rock.py:443): nothing happens
                 sj = acts[j] ? sj : st[j].s;
                 rec[j] = acts[j] ? rec[j] : a_taken[j];

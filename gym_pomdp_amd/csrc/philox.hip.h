@@ -74,6 +74,55 @@ __device__ __forceinline__ uint4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_
     return make_uint4(c0, c1, c2, c3);
 }
 
+// The same block for a loop that draws it once per step with counter words 0 and 3 fixed for the launch (the thread's quad,
+// the stream and block) and words 1, 2 (the call counter) wave-uniform.  Rounds 1 and 2 then split by what varies: the
+// products of the fixed words are the thread's for the whole launch (PhiloxFixed, computed before the loop), the products of
+// the call counter are wave-uniform — scalar multiplies and scalar xors — and the two xors that mix the two kinds leave the
+// vector unit eight rounds of work.  The generic form on the vector unit: about six more vector instructions per block.
+struct PhiloxFixed {
+    uint32_t a_lo;           // lo(M0 c0): counter word 3 after round 1
+    uint32_t d_hi, d_lo;     // M1 (hi(M0 c0) ^ c3 ^ k1): round 2's product of counter word 2
+};
+__device__ __forceinline__ PhiloxFixed philox_fixed(uint32_t c0, uint32_t c3, uint32_t k1)
+{
+    const uint64_t a = (uint64_t)0xD2511F53u * c0;
+    const uint64_t d = (uint64_t)0xCD9E8D57u * ((uint32_t)(a >> 32) ^ c3 ^ k1);
+    return PhiloxFixed{(uint32_t)a, (uint32_t)(d >> 32), (uint32_t)d};
+}
+// philox4x32_10(c0, c1, c2, c3, k0, k1) for the c0, c3 that `f` was made from; c1, c2, k0, k1 wave-uniform
+__device__ __forceinline__ uint4 philox4x32_10_fixed(const PhiloxFixed &f, uint32_t c1, uint32_t c2, uint32_t k0, uint32_t k1)
+{
+    // round 1: the call counter's product (scalar)
+    const uint64_t b = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t u0 = (uint32_t)(b >> 32) ^ c1 ^ k0;
+    // round 2: the product of the uniform word 0 (scalar); each new word xors one thread word with one scalar
+    const uint64_t c = (uint64_t)0xD2511F53u * u0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    uint32_t x0 = f.d_hi ^ ((uint32_t)b ^ k0);
+    uint32_t x2 = f.a_lo ^ ((uint32_t)(c >> 32) ^ k1);
+    uint32_t x1 = f.d_lo, x3 = (uint32_t)c;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    // round 3: word 3 is still uniform — its xor with the key word first
+    {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * x0;
+        const uint64_t p1 = (uint64_t)0xCD9E8D57u * x2;
+        const uint32_t n0 = __builtin_amdgcn_bitop3_b32((uint32_t)(p1 >> 32), x1, k0, 0x96);
+        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ (x3 ^ k1);
+        x1 = (uint32_t)p1; x3 = (uint32_t)p0; x0 = n0; x2 = n2;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+#pragma unroll
+    for (int r = 3; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * x0;
+        const uint64_t p1 = (uint64_t)0xCD9E8D57u * x2;
+        const uint32_t n0 = __builtin_amdgcn_bitop3_b32((uint32_t)(p1 >> 32), x1, k0, 0x96);
+        const uint32_t n2 = __builtin_amdgcn_bitop3_b32((uint32_t)(p0 >> 32), x3, k1, 0x96);
+        x1 = (uint32_t)p1; x3 = (uint32_t)p0; x0 = n0; x2 = n2;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return make_uint4(x0, x1, x2, x3);
+}
+
 // The key as a rare branch sees it: a copy the compiler cannot see through.  A Philox block's first rounds on the wave-uniform
 // counter words are cheap to speculate, and two rare branches of one step that draw the same block (a sensor tie, a reset tie)
 // make them a common subexpression: hoisted in front of both — into EVERY step (RockSample, one lane per thread: two scalar

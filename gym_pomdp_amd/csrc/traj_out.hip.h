@@ -96,13 +96,15 @@ struct SyntheticQuad {
     static constexpr bool TAPE = false;
     uint32_t glane0, n_act, k0, k1;
     uint64_t ta0;
+    PhiloxFixed fx;          // the quad's block of stream ACTION: its counter words 0 and 3 are the launch's (philox4x32_10_fixed)
     // (the policy shares the env's Philox key in every launch that takes these loops: the key words are the ENV key's, so that
     // the compiler keeps one copy of them in scalar registers — a second copy made Network's loop spill scalars)
     __device__ __forceinline__ SyntheticQuad(const TapeRef &, uint32_t, uint32_t glane0_, const RngKey &key0, const RngKey &akey0, uint32_t n_act_, int)
-        : glane0(glane0_), n_act(n_act_), k0(key0.k0), k1(key0.k1), ta0(((uint64_t)akey0.t_hi << 32) | akey0.t_lo) {}
+        : glane0(glane0_), n_act(n_act_), k0(key0.k0), k1(key0.k1), ta0(((uint64_t)akey0.t_hi << 32) | akey0.t_lo),
+          fx(philox_fixed(glane0_ >> 2, (uint32_t)POMDP_STREAM_ACTION << 24, key0.k1)) {}
     __device__ __forceinline__ uint4 block(uint64_t ta) const
     {
-        return philox4x32_10(glane0 >> 2, (uint32_t)ta, (uint32_t)(ta >> 32), (uint32_t)POMDP_STREAM_ACTION << 24, k0, k1);
+        return philox4x32_10_fixed(fx, (uint32_t)ta, (uint32_t)(ta >> 32), k0, k1);
     }
     // the actions of the call counter BEFORE akey0's: what pomdp_synthetic_actions would have written for the launch's first step
     __device__ __forceinline__ u32x4 first() const
