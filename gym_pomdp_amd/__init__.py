@@ -19,6 +19,7 @@ if not os.environ.get("GYM_POMDP_AMD_KEEP_ENV"):
 from . import spaces  # noqa: F401
 from .history import EpisodeStats, History, Returns, Transition  # noqa: F401
 from .envs import BattleShipEnv, NetworkEnv, RockEnv, StochasticRockEnv, TagEnv, TigerEnv  # noqa: F401
+from .particles import ParticleBelief  # noqa: F401
 
 __version__ = "0.1.0"
 

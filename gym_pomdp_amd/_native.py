@@ -16,7 +16,8 @@ INTREE_LIB_PATH = os.path.join(_PKG, "_lib", "libpomdp_hip.so")
 LIB_PATH = os.environ.get("GYM_POMDP_AMD_LIB") or INTREE_LIB_PATH
 # one object per translation unit (built in parallel), linked into one shared library
 UNITS = ["api.hip", "step_rock.hip", "step_other.hip", "fused_rock.hip", "fused_stochrock.hip", "fused_tag.hip",
-         "fused_battleship.hip", "fused_misc.hip", "planner.hip", "episodes.hip"]
+         "fused_battleship.hip", "fused_misc.hip", "planner.hip", "episodes.hip",
+         "particles.hip"]
 HEADERS = ["kernels_common.hip.h", "traj_out.hip.h", "step_impl.hip.h", "fused_impl.hip.h", "envs.hip.h", "envs_common.hip.h", "philox.hip.h",
            "envs/rock.hip.h", "envs/tag.hip.h", "envs/battleship.hip.h", "envs/tiger.hip.h", "envs/network.hip.h"]
 SOURCES = [os.path.join(_PKG, "csrc", f) for f in UNITS + HEADERS]
@@ -28,6 +29,7 @@ POMDP_FUSE_STEPS = 2
 POMDP_ROLLOUT_ALL_ACTIONS = 1
 LAYOUTS = {"columns": 0, "blocked": 1, "packed": 2, "narrow": 3}     # POMDP_LAYOUT_*
 POMDP_LAYOUT_RETURNS = 4                                              # pomdp_finish_episodes only
+PARTICLE_MATCH_REWARD = 1                                             # POMDP_PARTICLE_MATCH_REWARD
 FUSE_MAX_DEFAULT = 256
 ENV_KIND = {"rock": 0, "tag": 1, "battleship": 2, "tiger": 3, "network": 4}
 
@@ -41,6 +43,7 @@ SYMBOLS = [
     "pomdp_rock_belief_reset", "pomdp_rock_belief_refresh", "pomdp_rock_belief_update", "pomdp_rock_select_target", "pomdp_history_clear",
     "pomdp_history_append", "pomdp_preferred_actions", "pomdp_pick_actions", "pomdp_heuristic_steps",
     "pomdp_reset_where", "pomdp_finish_episodes",
+    "pomdp_particle_init", "pomdp_particle_update", "pomdp_plan_particles",
 ]
 
 
@@ -237,6 +240,12 @@ def lib():
     L.pomdp_plan.restype = ci
     L.pomdp_plan.argtypes = [ci, vp, vp, i64, i64, ci, C.c_double, ci, u64, u32, u64, vp, vp, vp, vp]
     L.pomdp_plan_reduce.restype = ci
+    L.pomdp_plan_particles.restype = ci
+    L.pomdp_plan_particles.argtypes = [ci, vp, vp, i64, ci, i64, ci, C.c_double, ci, u64, u32, u64, vp, vp, vp, vp]
+    L.pomdp_particle_init.restype = ci
+    L.pomdp_particle_init.argtypes = [ci, vp, vp, vp, vp, vp, i64, ci, u64, u32, u64, vp]
+    L.pomdp_particle_update.restype = ci
+    L.pomdp_particle_update.argtypes = [ci, vp, vp, vp, vp, vp, vp, vp, vp, i64, ci, ci, u64, u32, u64, vp]
     L.pomdp_plan_reduce.argtypes = [vp, vp, i64, i64, ci, vp, vp]
     L.pomdp_rock_belief_reset.restype = ci
     L.pomdp_rock_belief_reset.argtypes = [vp, vp, vp, i64, vp]

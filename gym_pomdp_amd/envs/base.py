@@ -635,7 +635,7 @@ class BatchedEnv(compat.EnvBase):
         out["terminated"] = out["terminated"].view(torch.bool)
         return out
 
-    def plan(self, depth, sims_per_root=1024, discount=None, all_actions=False, roots=None, out=None):
+    def plan(self, depth, sims_per_root=1024, discount=None, all_actions=False, roots=None, out=None, belief=None):
         """One planning pass of a POMCP-style caller over the live state (or `roots`): `sims_per_root` random rollouts of
         at most `depth` steps from every root (rollout()), reduced ON THE DEVICE to the roots' action values
         (pomdp_plan): {"q": float64 [R, n_actions] mean return by first action (0 where never tried), "visits": int32
@@ -645,7 +645,19 @@ class BatchedEnv(compat.EnvBase):
         CPU restatement reproduces them bit for bit.  Root r is global lane lane_offset + r and its simulation s is
         global lane (lane_offset + r) * sims_per_root + s: the draws — and with them q / visits / best — do not depend on
         how the roots are sharded, and whole roots never straddle a shard.  The call counter advances by `depth`.
-        `out`: the dict of an earlier call of the same shape, to reuse its buffers.  Asynchronous."""
+        `out`: the dict of an earlier call of the same shape, to reuse its buffers.  Asynchronous.
+        Without `belief` the roots are the TRUE states: flat Monte Carlo with the hidden state known.  `belief` (a
+        ParticleBelief of this env, particle_belief()): plan from its particles instead (pomdp_plan_particles) — particle p of
+        root r runs sims_per_root / P of the root's simulations (simulation p * (sims_per_root / P) + s, the same global lanes
+        as above); sims_per_root must be a multiple of P."""
+        if belief is not None:
+            if roots is not None:
+                raise ValueError("plan: roots= and belief= exclude each other")
+            if not belief._shape_ok(self):
+                raise ValueError("plan: the belief belongs to another env shape (%r)" % (belief,))
+            if int(sims_per_root) % belief.n_particles:
+                raise ValueError("plan: sims_per_root (%d) must be a multiple of the belief's particle count (%d)"
+                                 % (int(sims_per_root), belief.n_particles))
         st = self._state if roots is None else self._checked_state(roots, None, "plan")
         n_roots, sims, depth = st.shape[1], int(sims_per_root), int(depth)
         n, n_act = n_roots * sims, self.action_space.n
@@ -670,6 +682,14 @@ class BatchedEnv(compat.EnvBase):
         t0 = self._t
         self._t += depth
         with torch.cuda.device(self.device):
+            if belief is not None:
+                rc = self._lib.pomdp_plan_particles(
+                    _native.ENV_KIND[self.env_name], self._params_ref, belief.particles.data_ptr(), n_roots, belief.n_particles,
+                    sims, depth, float(self._discount if discount is None else discount),
+                    _native.POMDP_ROLLOUT_ALL_ACTIONS if all_actions else 0, self._seed, sim_lane0, t0, out["sim_ret"].data_ptr(),
+                    out["sim_first_action"].data_ptr(), C.byref(po), self._stream())
+                _native.check(rc, "pomdp_plan_particles")
+                return out
             rc = self._lib.pomdp_plan(
                 _native.ENV_KIND[self.env_name], self._params_ref, st.data_ptr(), n_roots, sims, depth,
                 float(self._discount if discount is None else discount), _native.POMDP_ROLLOUT_ALL_ACTIONS if all_actions else 0,
@@ -677,17 +697,36 @@ class BatchedEnv(compat.EnvBase):
             _native.check(rc, "pomdp_plan")
         return out
 
-    def plan_step(self, depth, sims_per_root=1024, discount=None, all_actions=False, out=None):
+    def plan_step(self, depth, sims_per_root=1024, discount=None, all_actions=False, out=None, belief=None):
         """One REAL step of every lane, planned: plan() from the live state, then step(best) — BASELINE.json configs[4]'s "1024-
         simulation rollout per real step".  Returns (ob, reward, done, info, plan dict).  A lane whose simulations took no
         step (best == -1: nothing legal to do, or depth == 0) is handed -1, which step() counts as an invalid action and
-        leaves untouched.  batch_size == 1: python scalars as step() returns them."""
-        p = self.plan(depth, sims_per_root, discount, all_actions, out=out)
+        leaves untouched.  batch_size == 1: python scalars as step() returns them.
+        `belief` (a ParticleBelief of this env): plan from its particles, step(best), then belief.update(best, ob, reward,
+        done) — the belief follows what the real step showed.  Needs auto_reset=False (an auto-reset step would not deliver
+        the fresh episode's observation).  Ended lanes are restarted by the caller, env and belief together:
+            ob = env.reset(where=done); belief.reset(ob, where=done)"""
+        if belief is not None and self._auto_reset:
+            raise ValueError("plan_step(belief=...) needs auto_reset=False: restart ended lanes with env.reset(where=done) and "
+                             "belief.reset(ob, where=done)")
+        p = self.plan(depth, sims_per_root, discount, all_actions, out=out, belief=belief)
         if self.batch_size == 1:
             a = int(p["best"].item())
             assert a >= 0, "plan_step: no simulation took a step"
-            return self.step(a) + (p,)
-        return self.step(p["best"]) + (p,)
+            res = self.step(a)
+            if belief is not None:
+                belief.update(a, res[0], res[1], res[2])
+            return res + (p,)
+        res = self.step(p["best"])
+        if belief is not None:
+            belief.update(p["best"], res[0], res[1], res[2])
+        return res + (p,)
+
+    def particle_belief(self, n_particles=256, seed=None):
+        """A ParticleBelief of n_particles particles per lane of this env (gym_pomdp_amd.particles); call its reset(ob) with
+        the observation of this env's reset() before planning from it."""
+        from ..particles import ParticleBelief
+        return ParticleBelief(self, n_particles, seed)
 
     def rollout_synthetic(self, steps, action_seed=None, actions=None, fuse=False):
         """`steps` consecutive step() calls under the synthetic uniform policy, issued from C

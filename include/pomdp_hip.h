@@ -89,7 +89,7 @@ enum {
 /* id of the word streams of one (seed, lane, t) */
 enum { POMDP_STREAM_STEP = 0, POMDP_STREAM_RESET = 1, POMDP_STREAM_STEP_SPACE = 2,
        POMDP_STREAM_RESET_SPACE = 3, POMDP_STREAM_ACTION = 4, POMDP_STREAM_ROLLOUT = 5, POMDP_STREAM_NEXT = 6,
-       POMDP_STREAM_STEP_LO = 7 };
+       POMDP_STREAM_STEP_LO = 7, POMDP_STREAM_PARTICLE = 8 };
 
 /* env kinds for the generic entry points */
 enum { POMDP_ENV_ROCK = 0, POMDP_ENV_TAG = 1, POMDP_ENV_BATTLESHIP = 2, POMDP_ENV_TIGER = 3, POMDP_ENV_NETWORK = 4 };
@@ -524,6 +524,54 @@ int pomdp_plan_reduce(const double *ret, const int32_t *first_action, int64_t n_
 int pomdp_plan(int env, const void *params, const uint32_t *root_state, int64_t n_roots, int64_t sims_per_root,
                int depth, double discount, int flags, uint64_t seed, uint32_t lane0, uint64_t t0,
                double *sim_ret, int32_t *sim_first_action, const pomdp_plan_out *out, void *stream);
+
+/* ---- particle beliefs: the belief a POMCP-style planner keeps per real episode ---------------------------------------
+ * pomdp_plan plans from the TRUE state of each root (flat Monte Carlo with the hidden state known).  A planner that does not
+ * know the hidden state keeps a set of P particles per root instead: after each real step it keeps the particles that, under
+ * the real action, reproduce the real observation, redraws the others from them, and plans from the particles.
+ * Layout: `particles` is uint32 [words][R * P], the packing of the env's state; column r * P + j is particle j of root r, and
+ * its global lane is g = lane0 + r * P + j (lane0 = lane_offset * P for a shard of roots starting at root lane_offset).
+ * pomdp_particle_init and pomdp_particle_update require P % 4 == 0, 4 <= P <= 4096, lane0 % 4 == 0 and lane0 + R * P <= 2^32
+ * (POMDP_E_BADARG otherwise); P % 4 keeps RockSample's quad-shared STEP blocks inside one root.  pomdp_plan_particles takes
+ * the same P rules but its lane0 is the simulations' (below).  Device buffers are the caller's; launches are
+ * asynchronous on `stream`; n_match is device int32 [R].
+ *
+ * Proposal of slot j of root r:
+ *   pomdp_particle_update: the result of pomdp_<env>_step(params, that column, action[r], ..., seed, lane g, t, flags = 0)
+ *     with the column's done flag clear — the same arithmetic and words as a call of that entry point on the whole R * P array
+ *     with action[r] repeated P times (no auto-reset; the state after a terminal step is the terminal state);
+ *   pomdp_particle_init: pomdp_<env>_reset at (seed, g, t), with its reset observation.
+ * Match rule: a proposal matches when its ob equals ob[r]; when done != NULL, its done flag equals (done[r] != 0); with
+ *   POMDP_PARTICLE_MATCH_REWARD, its reward equals reward[r] bit for bit (int32 or float per env, as step writes it).
+ *   In init, ob == NULL means that every proposal matches.
+ * Resample per root: let m be the number of matching slots and s_0 < ... < s_{m-1} those slots.
+ *   m >= 1: a matching slot keeps its own proposal; a non-matching slot j takes the proposal of s_k, k = (w_j * m) >> 32,
+ *           w_j = word 0 of block 0 of stream PARTICLE at (seed, g, t) (counter (g, t lo, t hi, POMDP_STREAM_PARTICLE << 24),
+ *           as the ROLLOUT words are built);
+ *   m == 0: every slot keeps its own proposal, unfiltered — the root is "depleted"; what to do about it is the caller's call;
+ *   n_match[r] = m.
+ * Roots that are not filtered: in update, a root whose action[r] lies outside [0, n_actions) (a plan's best == -1 included)
+ *   gets its particles copied unchanged and n_match[r] = -1; in init, a root with where[r] == 0 (where != NULL) is left
+ *   untouched and n_match[r] = -1.
+ * particles_out must not overlap particles_in (POMDP_E_BADARG).  reward is required with POMDP_PARTICLE_MATCH_REWARD; done
+ * may be NULL.  One launch per call: one 256-thread workgroup per root for P >= 256, 256 / P roots per workgroup below. */
+enum { POMDP_PARTICLE_MATCH_REWARD = 1 };
+int pomdp_particle_init(int env, const void *params, uint32_t *particles, const int32_t *ob, const uint8_t *where,
+                        int32_t *n_match, int64_t n_roots, int n_particles, uint64_t seed, uint32_t lane0, uint64_t t,
+                        void *stream);
+int pomdp_particle_update(int env, const void *params, const uint32_t *particles_in, uint32_t *particles_out,
+                          const int32_t *action, const int32_t *ob, const void *reward, const uint8_t *done,
+                          int32_t *n_match, int64_t n_roots, int n_particles, int flags, uint64_t seed, uint32_t lane0,
+                          uint64_t t, void *stream);
+/* Planning from particles: pomdp_rollout over the R * P particle columns as roots, sims_per_root / P simulations each
+ * (sims_per_root a multiple of P), followed by pomdp_plan_reduce over R roots x sims_per_root simulations.  Simulation s of
+ * particle p of root r is therefore simulation p * (sims_per_root / P) + s of root r, and its global lane is
+ * lane0 + r * sims_per_root + p * (sims_per_root / P) + s with lane0 = lane_offset * sims_per_root, exactly as in pomdp_plan:
+ * q / visits / best do not depend on how the roots are sharded.  Requires sims_per_root % P == 0 (sims_per_root >= P),
+ * lane0 % 4 == 0 and lane0 + R * sims_per_root <= 2^32; arguments otherwise as pomdp_plan's. */
+int pomdp_plan_particles(int env, const void *params, const uint32_t *particles, int64_t n_roots, int n_particles,
+                         int64_t sims_per_root, int depth, double discount, int flags, uint64_t seed, uint32_t lane0,
+                         uint64_t t0, double *sim_ret, int32_t *sim_first_action, const pomdp_plan_out *out, void *stream);
 
 /* ---- heuristic-policy support --------------------------- */
 /* RockSample's per-rock side statistics — the Rock fields count, measured, lkv, lkw, prob_valuable of rock.py:78-86,
