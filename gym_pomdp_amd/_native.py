@@ -17,8 +17,8 @@ LIB_PATH = os.environ.get("GYM_POMDP_AMD_LIB") or INTREE_LIB_PATH
 # one object per translation unit (built in parallel), linked into one shared library
 UNITS = ["api.hip", "step_rock.hip", "step_other.hip", "fused_rock.hip", "fused_stochrock.hip", "fused_tag.hip",
          "fused_battleship.hip", "fused_misc.hip", "planner.hip", "episodes.hip",
-         "particles.hip"]
-HEADERS = ["kernels_common.hip.h", "traj_out.hip.h", "step_impl.hip.h", "fused_impl.hip.h", "envs.hip.h", "envs_common.hip.h", "philox.hip.h",
+         "particles.hip", "planner_preferred.hip"]
+HEADERS = ["kernels_common.hip.h", "planner_common.hip.h", "traj_out.hip.h", "step_impl.hip.h", "fused_impl.hip.h", "envs.hip.h", "envs_common.hip.h", "philox.hip.h",
            "envs/rock.hip.h", "envs/tag.hip.h", "envs/battleship.hip.h", "envs/tiger.hip.h", "envs/network.hip.h"]
 SOURCES = [os.path.join(_PKG, "csrc", f) for f in UNITS + HEADERS]
 HEADER = os.path.join(_REPO, "include", "pomdp_hip.h")
@@ -44,6 +44,7 @@ SYMBOLS = [
     "pomdp_history_append", "pomdp_preferred_actions", "pomdp_pick_actions", "pomdp_heuristic_steps",
     "pomdp_reset_where", "pomdp_finish_episodes",
     "pomdp_particle_init", "pomdp_particle_update", "pomdp_plan_particles",
+    "pomdp_rollout_preferred_workspace", "pomdp_rollout_preferred", "pomdp_plan_preferred",
 ]
 
 
@@ -242,6 +243,12 @@ def lib():
     L.pomdp_plan_reduce.restype = ci
     L.pomdp_plan_particles.restype = ci
     L.pomdp_plan_particles.argtypes = [ci, vp, vp, i64, ci, i64, ci, C.c_double, ci, u64, u32, u64, vp, vp, vp, vp]
+    L.pomdp_rollout_preferred_workspace.restype = i64
+    L.pomdp_rollout_preferred_workspace.argtypes = [ci, vp, i64, i64]
+    L.pomdp_rollout_preferred.restype = ci
+    L.pomdp_rollout_preferred.argtypes = [ci, vp, vp, i64, ci, i64, ci, C.c_double, vp, vp, vp, vp, u64, u32, u64, vp, vp, vp, vp, vp, vp]
+    L.pomdp_plan_preferred.restype = ci
+    L.pomdp_plan_preferred.argtypes = [ci, vp, vp, i64, ci, i64, ci, C.c_double, vp, vp, vp, vp, u64, u32, u64, vp, vp, vp, vp]
     L.pomdp_particle_init.restype = ci
     L.pomdp_particle_init.argtypes = [ci, vp, vp, vp, vp, vp, i64, ci, u64, u32, u64, vp]
     L.pomdp_particle_update.restype = ci

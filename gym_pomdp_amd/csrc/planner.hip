@@ -1,6 +1,7 @@
 // planner.hip — planner hooks: _generate_legal, _compute_prob, fused rollouts, side statistics, History, _generate_preferred, the heuristic-policy loop.
 // Part of libpomdp_hip.so; built by gym_pomdp_amd/_native.py (hipcc --offload-arch=gfx950 -O3 -std=c++17 -c, one object per file).
 #include "kernels_common.hip.h"
+#include "planner_common.hip.h"
 
 namespace pomdp {
 
@@ -194,15 +195,6 @@ __global__ __launch_bounds__(BLOCK) void history_append_kernel(pomdp_history h, 
     if (h.head) h.head[i] = head;
 }
 
-// envs whose _generate_preferred reads extra LDS tables fill them with Env::stage_policy
-template <class Env, class = void> struct HasPolicyTables : std::false_type {};
-template <class Env> struct HasPolicyTables<Env, std::void_t<decltype(&Env::stage_policy)>> : std::true_type {};
-template <class Env>
-static __device__ __forceinline__ void stage_policy_tables(typename Env::Shared &sh, const typename Env::Params &p)
-{
-    if constexpr (HasPolicyTables<Env>::value) Env::stage_policy(sh, p, (int)threadIdx.x);
-}
-
 template <class Env>
 __global__ __launch_bounds__(BLOCK) void preferred_kernel(const typename Env::Params p, const uint32_t *__restrict__ state,
                                                           pomdp_rock_belief b, pomdp_history h, int32_t *__restrict__ list,
@@ -268,37 +260,6 @@ static __device__ __forceinline__ void heuristic_belief_update(const typename En
     BeliefOps<Env>::update(sh, p, st, a, o, b, n, i, ck);
 }
 
-
-// _generate_legal() as the rollout loop uses it — the list's length, then its idx-th entry: envs that derive both from one
-// intermediate form (Env::Legal, Env::legal_set, Env::legal_pick) compute it once per step, the others go through
-// legal_count / legal_nth
-template <class Env, class = void> struct LegalOf {
-    struct Set { int count; };
-    static __device__ __forceinline__ Set make(const typename Env::Shared &sh, const typename Env::Params &p,
-                                               const typename Env::State &st, bool skip)
-    {
-        return Set{skip ? 0 : Env::legal_count(sh, p, st)};
-    }
-    static __device__ __forceinline__ int pick(const typename Env::Shared &sh, const typename Env::Params &p,
-                                               const typename Env::State &st, const Set &, int idx)
-    {
-        return Env::legal_nth(sh, p, st, idx);
-    }
-};
-template <class Env> struct LegalOf<Env, std::void_t<typename Env::Legal>> {
-    using Set = typename Env::Legal;
-    static __device__ __forceinline__ Set make(const typename Env::Shared &sh, const typename Env::Params &p,
-                                               const typename Env::State &st, bool skip)
-    {
-        if (skip) return Set{};
-        return Env::legal_set(sh, p, st);
-    }
-    static __device__ __forceinline__ int pick(const typename Env::Shared &sh, const typename Env::Params &,
-                                               const typename Env::State &, const Set &L, int idx)
-    {
-        return Env::legal_pick(sh, L, idx);
-    }
-};
 
 // k heuristic-policy steps in one launch: per step choice(_generate_preferred(history)) -> step -> side statistics ->
 // history.append, i.e. preferred_kernel + pick_actions_kernel + step_kernel + belief_update_kernel +
@@ -456,11 +417,6 @@ void heuristic_steps_kernel(const typename Env::Params p, uint32_t *__restrict__
     if (RING) st_stream(h.head + i, (int32_t)head);                            // without a window `head` never moves
     if (R.ret) { R.ret[i] = ret; R.disc[i] = disc; }
 }
-
-// RockSample's rollouts read the lane step from the (position, action) table of the fused loops, built once per launch
-// (2.61 -> 2.73e11 steps/s on (15,15), 2.72 -> 2.80e11 on (7,8))
-template <class Env, class = void> struct ROLLOUT_TAB : std::false_type {};
-template <class Env> struct ROLLOUT_TAB<Env, typename std::enable_if<Env::QUAD_SENSOR && Env::QUAD_TAB>::type> : std::true_type {};
 
 // Lane i simulates from root state column i / sims_per_root for up to `depth` steps: the state lives in registers
 // and nothing is written but the per-lane results.  Random words, four steps at a time:
@@ -682,16 +638,6 @@ static int launch_rollout(const typename Env::Params &p, const uint32_t *state, 
                        n_steps, first_action, last_ob, terminated);
     return (int)hipGetLastError();
 }
-static bool belief_ok(const pomdp_rock_belief *b)
-{
-    return b && b->count && b->measured && b->lkv && b->lkw && b->prob_valuable && b->check_ok;
-}
-static bool history_ok(const pomdp_history *h, bool rock)
-{
-    if (!(h && h->size && h->last_action && h->last_ob && (!rock || (h->total_sample && h->total_move && h->move_ok)))) return false;
-    if (h->max_size < -1 || h->max_size > 0x7FFFFFFE) return false;           // any window the caller has a (max_size + 1) x n byte ring for
-    return h->max_size < 0 || !rock || (h->ring && h->head);                   // a bounded RockSample history keeps its window
-}
 static const pomdp_rock_belief NO_BELIEF = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 
 template <class Env>
@@ -784,11 +730,6 @@ int pomdp_rollout(int env, const void *params, const uint32_t *root_state, int64
         return launch_rollout<E>(p, root_state, n_roots, sims_per_root, depth, discount, flags, seed, lane0, t0, ret, n_steps,
                                  first_action, last_ob, terminated, stream);
     });
-}
-
-static bool plan_out_ok(const pomdp_plan_out *o, int n_act)
-{
-    return o && o->q && o->visits && o->best && n_act >= 1 && n_act <= 255 && o->stride >= n_act;
 }
 
 int pomdp_plan_reduce(const double *ret, const int32_t *first_action, int64_t n_roots, int64_t sims_per_root, int n_actions,

@@ -600,14 +600,53 @@ class BatchedEnv(compat.EnvBase):
             return float(self.compute_prob([int(action)], [int(ob)], next_state).item())
         return self.compute_prob(action, ob, next_state)
 
-    def rollout(self, depth, sims_per_root=1, roots=None, discount=None, all_actions=False, lane_offset=None, out=None):
+    def _preferred_policy(self, what, policy, history, all_actions, roots):
+        """The checks `policy=` shares between rollout / plan / plan_step -> True when the preferred-policy kernel runs.
+        A RockSample env built without use_heuristic answers _generate_preferred with the legal list (rock.py:294-295): its
+        preferred rollout IS the uniform one and needs neither history nor side statistics."""
+        if policy == "uniform":
+            if history is not None:
+                raise ValueError("%s: history= goes with policy='preferred'" % what)
+            return False
+        if policy != "preferred":
+            raise ValueError("%s: policy must be 'uniform' or 'preferred', got %r" % (what, policy))
+        if all_actions or roots is not None:
+            raise ValueError("%s: policy='preferred' excludes all_actions=True and roots=: the side statistics and the history "
+                             "describe the live lanes" % what)
+        if self.env_name == "rock" and not self._use_heuristic:
+            return False
+        if history is None or getattr(history, "_env", None) is not self:
+            raise ValueError("%s: policy='preferred' needs history=, a gym_pomdp_amd.History of this env" % what)
+        if history._max_size is not None:
+            raise ValueError("%s: policy='preferred' needs an unbounded History (a simulation would have to carry the window "
+                             "of History(max_size=%d))" % (what, history._max_size))
+        if self.env_name == "rock" and history.prev_ob is None:
+            raise ValueError("History was built without the current observation: History(env, observation=ob)")
+        return True
+
+    def _preferred_args(self, history, n_sims, out):
+        """(belief, history, prev_ob, workspace) of pomdp_rollout_preferred; the workspace is cached in `out`"""
+        if self.env_name != "rock":
+            return None, history._ref, None, None
+        ws = out.get("_workspace")
+        nbytes = 32 * self.num_rocks * n_sims
+        if ws is None or ws.numel() != nbytes:
+            ws = out["_workspace"] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return self._belief_ref(), history._ref, history.prev_ob.data_ptr(), ws.data_ptr()
+
+    def rollout(self, depth, sims_per_root=1, roots=None, discount=None, all_actions=False, lane_offset=None, out=None,
+                policy="uniform", history=None):
         """Random rollouts from `roots` (packed states int32 [state_words, R]; default: the live state):
         R * sims_per_root independent simulations of at most `depth` steps under a uniform policy over
         `_generate_legal()` (or over all actions), discounted by `discount` (default: the env's
         `_discount`).  Neither `roots` nor the live state is modified; the call counter advances by
         `depth`.  Returns a dict of per-simulation tensors: ret float64, n_steps, first_action, last_ob
         int32, terminated bool — simulation i belongs to root i // sims_per_root.  `out`: the dict of an earlier
-        call of the same shape, to reuse its buffers."""
+        call of the same shape, to reuse its buffers.
+        `policy="preferred"` with `history=` (an unbounded History of this env): every simulation picks from
+        `_generate_preferred(history)` instead — the env's own rollout policy, as POMCP uses it — starting from the live
+        lanes' side statistics and history and keeping its own copies of them as it goes (pomdp_rollout_preferred)."""
+        preferred = self._preferred_policy("rollout", policy, history, all_actions, roots)
         st = self._state if roots is None else self._checked_state(roots, None, "rollout")
         n_roots = st.shape[1]
         n = n_roots * int(sims_per_root)
@@ -623,6 +662,17 @@ class BatchedEnv(compat.EnvBase):
                        terminated=torch.empty(n, dtype=torch.uint8, device=self.device))
         else:                              # a dict returned by an earlier call of the same shape: buffers are reused
             out["terminated"] = out["terminated"].view(torch.uint8)
+        if preferred:
+            with torch.cuda.device(self.device):
+                rc = self._lib.pomdp_rollout_preferred(
+                    _native.ENV_KIND[self.env_name], self._params_ref, st.data_ptr(), n_roots, 1, int(sims_per_root), int(depth),
+                    float(self._discount if discount is None else discount), *self._preferred_args(history, n, out), self._seed,
+                    self.lane_offset if lane_offset is None else int(lane_offset), t0, out["ret"].data_ptr(),
+                    out["n_steps"].data_ptr(), out["first_action"].data_ptr(), out["last_ob"].data_ptr(),
+                    out["terminated"].data_ptr(), self._stream())
+                _native.check(rc, "pomdp_rollout_preferred")
+            out["terminated"] = out["terminated"].view(torch.bool)
+            return out
         with torch.cuda.device(self.device):
             rc = self._lib.pomdp_rollout(
                 _native.ENV_KIND[self.env_name], self._params_ref, st.data_ptr(), n_roots, int(sims_per_root),
@@ -635,7 +685,8 @@ class BatchedEnv(compat.EnvBase):
         out["terminated"] = out["terminated"].view(torch.bool)
         return out
 
-    def plan(self, depth, sims_per_root=1024, discount=None, all_actions=False, roots=None, out=None, belief=None):
+    def plan(self, depth, sims_per_root=1024, discount=None, all_actions=False, roots=None, out=None, belief=None,
+             policy="uniform", history=None):
         """One planning pass of a POMCP-style caller over the live state (or `roots`): `sims_per_root` random rollouts of
         at most `depth` steps from every root (rollout()), reduced ON THE DEVICE to the roots' action values
         (pomdp_plan): {"q": float64 [R, n_actions] mean return by first action (0 where never tried), "visits": int32
@@ -649,7 +700,11 @@ class BatchedEnv(compat.EnvBase):
         Without `belief` the roots are the TRUE states: flat Monte Carlo with the hidden state known.  `belief` (a
         ParticleBelief of this env, particle_belief()): plan from its particles instead (pomdp_plan_particles) — particle p of
         root r runs sims_per_root / P of the root's simulations (simulation p * (sims_per_root / P) + s, the same global lanes
-        as above); sims_per_root must be a multiple of P."""
+        as above); sims_per_root must be a multiple of P.
+        `policy="preferred"` with `history=` (an unbounded History of this env): the simulations roll out under
+        `_generate_preferred(history)` as in rollout() (pomdp_plan_preferred), from the true states or from `belief`'s
+        particles; the side statistics and the history are the live lanes' either way."""
+        preferred = self._preferred_policy("plan", policy, history, all_actions, roots)
         if belief is not None:
             if roots is not None:
                 raise ValueError("plan: roots= and belief= exclude each other")
@@ -681,6 +736,16 @@ class BatchedEnv(compat.EnvBase):
                                                     value=out["value"].data_ptr(), stride=n_act, reserved=0)
         t0 = self._t
         self._t += depth
+        if preferred:
+            with torch.cuda.device(self.device):
+                rc = self._lib.pomdp_plan_preferred(
+                    _native.ENV_KIND[self.env_name], self._params_ref,
+                    st.data_ptr() if belief is None else belief.particles.data_ptr(), n_roots,
+                    1 if belief is None else belief.n_particles, sims, depth,
+                    float(self._discount if discount is None else discount), *self._preferred_args(history, n, out), self._seed,
+                    sim_lane0, t0, out["sim_ret"].data_ptr(), out["sim_first_action"].data_ptr(), C.byref(po), self._stream())
+                _native.check(rc, "pomdp_plan_preferred")
+            return out
         with torch.cuda.device(self.device):
             if belief is not None:
                 rc = self._lib.pomdp_plan_particles(
@@ -697,7 +762,8 @@ class BatchedEnv(compat.EnvBase):
             _native.check(rc, "pomdp_plan")
         return out
 
-    def plan_step(self, depth, sims_per_root=1024, discount=None, all_actions=False, out=None, belief=None):
+    def plan_step(self, depth, sims_per_root=1024, discount=None, all_actions=False, out=None, belief=None,
+                  policy="uniform", history=None):
         """One REAL step of every lane, planned: plan() from the live state, then step(best) — BASELINE.json configs[4]'s "1024-
         simulation rollout per real step".  Returns (ob, reward, done, info, plan dict).  A lane whose simulations took no
         step (best == -1: nothing legal to do, or depth == 0) is handed -1, which step() counts as an invalid action and
@@ -705,21 +771,32 @@ class BatchedEnv(compat.EnvBase):
         `belief` (a ParticleBelief of this env): plan from its particles, step(best), then belief.update(best, ob, reward,
         done) — the belief follows what the real step showed.  Needs auto_reset=False (an auto-reset step would not deliver
         the fresh episode's observation).  Ended lanes are restarted by the caller, env and belief together:
-            ob = env.reset(where=done); belief.reset(ob, where=done)"""
+            ob = env.reset(where=done); belief.reset(ob, where=done)
+        `policy="preferred"` with `history=`: plan under the env's preferred-action policy, then keep the agent's knowledge in
+        step with the real step: step() updates RockSample's side statistics (pomdp_rock_belief_update), the transition
+        (history.prev_ob, best, reward, ob, done) is appended to `history` (pomdp_history_append) and history.prev_ob becomes
+        ob — next to belief.update(...) when `belief` is given.  Needs auto_reset=False for the same reason; the caller
+        restarts ended lanes with env.reset(where=done), belief.reset(ob, where=done), history.clear(where=done) and
+        history.prev_ob[done] = ob[done]."""
         if belief is not None and self._auto_reset:
             raise ValueError("plan_step(belief=...) needs auto_reset=False: restart ended lanes with env.reset(where=done) and "
                              "belief.reset(ob, where=done)")
-        p = self.plan(depth, sims_per_root, discount, all_actions, out=out, belief=belief)
+        if policy == "preferred" and self._auto_reset:
+            raise ValueError("plan_step(policy='preferred') needs auto_reset=False: restart ended lanes with env.reset(where=done) "
+                             "and history.clear(where=done)")
+        p = self.plan(depth, sims_per_root, discount, all_actions, out=out, belief=belief, policy=policy, history=history)
+        a = p["best"]
         if self.batch_size == 1:
-            a = int(p["best"].item())
+            a = int(a.item())
             assert a >= 0, "plan_step: no simulation took a step"
-            res = self.step(a)
-            if belief is not None:
-                belief.update(a, res[0], res[1], res[2])
-            return res + (p,)
-        res = self.step(p["best"])
+        res = self.step(a)
+        if history is not None:
+            from ..history import Transition
+            history.append(Transition(history.prev_ob, a, res[1], res[0], res[2]), auto_reset=False)
+            if history.prev_ob is not None:
+                history.prev_ob.copy_(torch.as_tensor(res[0], device=self.device).to(torch.int32).reshape(self.batch_size))
         if belief is not None:
-            belief.update(p["best"], res[0], res[1], res[2])
+            belief.update(a, res[0], res[1], res[2])
         return res + (p,)
 
     def particle_belief(self, n_particles=256, seed=None):

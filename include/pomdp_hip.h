@@ -673,6 +673,49 @@ int pomdp_heuristic_steps(int env, const void *params, uint32_t *state, const po
                           const pomdp_returns *returns, int64_t n, uint64_t seed, uint32_t lane0, uint64_t t0,
                           int64_t k_steps, int flags, void *stream);
 
+/* ---- rollouts under the env's preferred-action policy (added to ABI 15: new entry points only, nothing existing changes) --
+ * pomdp_rollout with a different list to pick from: POMCP's rollout policy.  The lanes, the ROLLOUT word k that picks, the
+ * STEP words at t0 + k, the float64 return (separate multiply and add) and the outputs ret / n_steps / first_action /
+ * last_ob / terminated are pomdp_rollout's.  What is new is read-only and indexed by REAL root r < n_roots — it describes
+ * what the agent of root r has seen:
+ *   b        RockSample / StochasticRock only (NULL otherwise): the side statistics, arrays [num_rocks][n_roots];
+ *   h        the history words, arrays [n_roots] and [num_rocks][n_roots]; max_size must be -1 — a bounded history is refused
+ *            with POMDP_E_BADARG: a simulation would have to carry the window;
+ *   prev_ob  int32 [n_roots], the observation each root saw last (History.prev_ob); RockSample only (may be NULL otherwise).
+ * `state` is uint32 [words][n_roots * n_particles].  n_particles = 1: the roots' TRUE states, column r, as in pomdp_rollout /
+ * pomdp_plan.  n_particles = P > 1: particle p = (i % sims_per_root) / (sims_per_root / P) of root r, column r * P + p — the
+ * lanes of pomdp_plan_particles; sims_per_root must be a multiple of P.  The policy inputs stay per root r either way.
+ * Simulation i of root r = i / sims_per_root (global lane lane0 + i) starts from its state column and from PRIVATE copies of
+ * root r's statistics, history words and prev_ob, and for k = 0 .. depth-1, while not done:
+ *   1. list = _generate_preferred(history): exactly what pomdp_preferred_actions returns for that state, statistics and
+ *      history — ascending action order; an empty list falls back to _generate_legal(); for Tiger, Network and BattleShip
+ *      the list is the legal list, as it is there; for RockSample the heuristic always applies (use_heuristic is a switch
+ *      of the host mirror: an env built without it runs pomdp_rollout);
+ *   2. a = list[(w * len(list)) >> 32], w = word k of stream ROLLOUT at (seed, lane, t0);
+ *   3. (ob, r, done) = step(a) on stream STEP at (seed, lane, t0 + k), no auto-reset;  ret += disc * r;  disc *= discount;
+ *   4. the private copies are updated as one non-auto-reset step of pomdp_heuristic_steps updates a live lane: history
+ *      size / last_action / last_ob and both per-rock sums (the prev_ob == BAD rule included); the side statistics on a
+ *      CHECK with ob != 0 that did not end the episode; prev_ob <- ob.
+ * Nothing of the roots is written.  Results depend neither on the launch geometry nor on how roots are sharded (lane0 % 4
+ * == 0, whole roots per shard, as for pomdp_plan).
+ * workspace: device, pomdp_rollout_preferred_workspace(...) = 32 * num_rocks * n_roots * sims_per_root bytes (0 for the
+ * envs without rocks: pass NULL), 16-byte aligned, the caller's; it need not be initialised and its contents afterwards are
+ * unspecified.  A simulation keeps there the per-rock entries its own CHECKs changed (copy on first touch: the first
+ * CHECK of rock j reads root r's entry, later ones the simulation's own).
+ * One launch; for the envs whose preferred list is the legal list it is pomdp_rollout's kernel over the state columns. */
+int64_t pomdp_rollout_preferred_workspace(int env, const void *params, int64_t n_roots, int64_t sims_per_root);
+int pomdp_rollout_preferred(int env, const void *params, const uint32_t *state, int64_t n_roots, int n_particles,
+                            int64_t sims_per_root, int depth, double discount, const pomdp_rock_belief *b,
+                            const pomdp_history *h, const int32_t *prev_ob, void *workspace, uint64_t seed, uint32_t lane0,
+                            uint64_t t0, double *ret, int32_t *n_steps, int32_t *first_action, int32_t *last_ob,
+                            uint8_t *terminated, void *stream);
+/* pomdp_rollout_preferred followed by pomdp_plan_reduce (unchanged) over n_roots roots x sims_per_root simulations: what
+ * pomdp_plan (n_particles = 1) and pomdp_plan_particles (n_particles = P) are to pomdp_rollout. */
+int pomdp_plan_preferred(int env, const void *params, const uint32_t *state, int64_t n_roots, int n_particles,
+                         int64_t sims_per_root, int depth, double discount, const pomdp_rock_belief *b, const pomdp_history *h,
+                         const int32_t *prev_ob, void *workspace, uint64_t seed, uint32_t lane0, uint64_t t0, double *sim_ret,
+                         int32_t *sim_first_action, const pomdp_plan_out *out, void *stream);
+
 int         pomdp_abi_version(void);
 const char *pomdp_error_string(int code);
 /* introspection: the kernel (name<template arguments>, as a profiler shows it) that the calling thread's most recent
