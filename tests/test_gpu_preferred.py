@@ -1,7 +1,9 @@
 """Rollouts under the env's preferred-action policy on the GPU (pomdp_rollout_preferred / pomdp_plan_preferred;
 rollout / plan / plan_step(policy="preferred", history=...)) against the contract's CPU restatement
 (tests/preferred_rollout_restatement.py), bit for bit.  Each case is one launch sequence.  test_preferred_host.py shows on the
-oracle that the roots used here are not vacuous inputs."""
+oracle that the roots used here are not vacuous inputs: the prepared ones (reset() plus real heuristic steps) and the
+CONSTRUCTED ones (rr.construct_roots: statistics at every threshold the policy tests, empty histories, closed rocks), whose
+simulations take every branch of the policy and of the copy-on-first-touch workspace."""
 import os
 import sys
 
@@ -12,6 +14,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import preferred_rollout_restatement as rr  # noqa: E402
 from test_preferred_host import GPU_CASES, GPU_IDS, SEED, ROOTS, SIMS, DEPTH  # noqa: E402
+from test_preferred_host import CONSTRUCTED, C_IDS, C_ROOTS, C_SIMS, C_DEPTH, ROOT_SEED  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -70,19 +73,114 @@ def roots_of(e, hist):
     return belief, history, np_(hist.prev_ob).copy()
 
 
-def raw_rollout(e, hist, states, R, P, sims, depth, lane0, t0):
-    """pomdp_rollout_preferred itself, for the five per-simulation outputs from particles as well"""
+def raw_rollout(e, hist, states, R, P, sims, depth, lane0, t0, workspace=None, out=None, refused=False):
+    """pomdp_rollout_preferred itself, for the five per-simulation outputs from particles as well.  workspace: the caller's own
+    (a uint8 tensor) in place of env's cached one; out: buffers to write into; refused: the call must return POMDP_E_BADARG"""
     from gym_pomdp_amd import _native
     n = R * sims
-    out = dict(ret=torch.empty(n, dtype=torch.float64, device=e.device), terminated=torch.empty(n, dtype=torch.uint8, device=e.device))
-    for k in ("n_steps", "first_action", "last_ob"):
-        out[k] = torch.empty(n, dtype=torch.int32, device=e.device)
+    if out is None:
+        out = dict(ret=torch.empty(n, dtype=torch.float64, device=e.device), terminated=torch.empty(n, dtype=torch.uint8, device=e.device))
+        for k in ("n_steps", "first_action", "last_ob"):
+            out[k] = torch.empty(n, dtype=torch.int32, device=e.device)
+    args = list(e._preferred_args(hist, n, out))
+    if workspace is not None:
+        assert workspace.numel() == 32 * e.num_rocks * n and workspace.data_ptr() % 16 == 0
+        args[3] = workspace.data_ptr()
     with torch.cuda.device(e.device):
         rc = e._lib.pomdp_rollout_preferred(_native.ENV_KIND[e.env_name], e._params_ref, states.data_ptr(), R, P, sims, depth,
-                                            float(e._discount), *e._preferred_args(hist, n, out), e._seed, lane0, t0,
+                                            float(e._discount), *args, e._seed, lane0, t0,
                                             *[out[k].data_ptr() for k in FIVE], e._stream())
+    if refused:
+        assert rc == -1, rc                                             # POMDP_E_BADARG
+        return out
     _native.check(rc, "pomdp_rollout_preferred")
     return out
+
+
+def raw_plan(e, hist, states, R, P, sims, depth, lane0, t0):
+    """pomdp_plan_preferred itself, as plan() calls it, for a particle count ParticleBelief does not build (it wants a multiple
+    of 4; the C ABI takes any P that divides the simulations) -> plan()'s six outputs"""
+    import ctypes as C
+    from gym_pomdp_amd import _native
+    n, n_act, dev = R * sims, e.action_space.n, e.device
+    out = dict(q=torch.zeros((R, n_act), dtype=torch.float64, device=dev), visits=torch.zeros((R, n_act), dtype=torch.int32, device=dev),
+               best=torch.empty(R, dtype=torch.int32, device=dev), value=torch.empty(R, dtype=torch.float64, device=dev),
+               sim_ret=torch.empty(n, dtype=torch.float64, device=dev), sim_first_action=torch.empty(n, dtype=torch.int32, device=dev))
+    po = _native.PlanOut(q=out["q"].data_ptr(), visits=out["visits"].data_ptr(), best=out["best"].data_ptr(),
+                         value=out["value"].data_ptr(), stride=n_act, reserved=0)
+    with torch.cuda.device(dev):
+        rc = e._lib.pomdp_plan_preferred(_native.ENV_KIND[e.env_name], e._params_ref, states.data_ptr(), R, P, sims, depth,
+                                         float(e._discount), *e._preferred_args(hist, n, out), e._seed, lane0, t0,
+                                         out["sim_ret"].data_ptr(), out["sim_first_action"].data_ptr(), C.byref(po), e._stream())
+    _native.check(rc, "pomdp_plan_preferred")
+    return out
+
+
+def columns_of(e, b):
+    """the state columns a launch starts from: the live states, a ParticleBelief's particles, or a tensor of columns"""
+    return e._state if b is None else b if torch.is_tensor(b) else b.particles
+
+
+def constructed(env, kw, R, prep, P=1, lane_offset=0, root_seed=ROOT_SEED):
+    """prepared() with the statistics overwritten by rr.construct_roots, on the GPU and as the restatement takes them
+    -> (oracle env, env, History, ParticleBelief | None); for a P that ParticleBelief does not build, in its place the tensor
+    of the first P of every root's four particles, int32 [words, R * P], which only the C ABI takes"""
+    from oracle import oracle_lib as ol
+    o = ol.OracleEnv(env, **kw)
+    e, hist, b = prepared(env, kw, R, prep, P if P % 4 == 0 or P == 1 else 4, lane_offset)
+    if b is not None and b.n_particles != P:
+        b = b.particles.reshape(-1, R, 4)[:, :, :P].reshape(-1, R * P).contiguous()
+    belief, history, pob = roots_of(e, hist)
+    cols = u32(columns_of(e, b))
+    belief, history, pob = rr.construct_roots(o, cols.reshape(o.words, R * P), P, belief, history, pob, root_seed)
+    rr.put_roots(e, hist, belief, history, pob)
+    got = roots_of(e, hist)                                             # what was written is what is read back
+    assert all(np.array_equal(got[1][k], history[k]) for k in history) and np.array_equal(got[2], pob)
+    assert belief is None or all(got[0][k].tobytes() == belief[k].tobytes() for k in belief)
+    return o, e, hist, b
+
+
+def check_launch(o, e, hist, b, R, P, sims, depth, lane_offset, counter, ctx):
+    """one launch of each entry point from the env's roots against the restatement: the five raw outputs, plan()'s six, rollout()
+    from the true states, and that nothing of the roots is written -> the restatement's stats"""
+    from oracle import oracle_lib as ol
+    if counter is not None:
+        e.call_counter = counter
+    t0, lane0 = e.call_counter, lane_offset * sims
+    belief, history, pob = roots_of(e, hist)
+    state0 = u32(e.state).reshape(o.words, R).copy()
+    states = state0 if b is None else u32(columns_of(e, b)).copy()
+    want_plan, want = rr.plan(o, states, belief, history, pob, R, P, sims, depth, e._discount, e._seed, lane0, t0, nthreads=ol.max_threads(),
+                              counters=True)
+    got = raw_rollout(e, hist, columns_of(e, b), R, P, sims, depth, lane0, t0)
+    for k in FIVE:
+        assert np.array_equal(np_(got[k]), want[k]), ctx + (k,)
+    assert np_(got["ret"]).tobytes() == want["ret"].tobytes(), ctx
+    if torch.is_tensor(b):
+        p = raw_plan(e, hist, b, R, P, sims, depth, lane0, t0)
+    else:
+        p = e.plan(depth, sims, policy="preferred", history=hist, belief=b)
+        assert e.call_counter == t0 + depth
+    assert np_(p["sim_ret"]).tobytes() == want["ret"].tobytes() and np.array_equal(np_(p["sim_first_action"]), want["first_action"]), ctx
+    assert np_(p["q"]).tobytes() == want_plan["q"].tobytes() and np_(p["value"]).tobytes() == want_plan["value"].tobytes(), ctx
+    assert np.array_equal(np_(p["visits"]), want_plan["visits"]) and np.array_equal(np_(p["best"]), want_plan["best"]), ctx
+    if P == 1:                                                          # rollout() from the live state: the same lanes when lane_offset * sims == lane0
+        e.call_counter = t0
+        r = e.rollout(depth, sims, lane_offset=lane0, policy="preferred", history=hist)
+        for k in FIVE:
+            assert np.array_equal(np_(r[k]).astype(want[k].dtype), want[k]), ctx + (k,)
+        assert np_(r["ret"]).tobytes() == want["ret"].tobytes(), ctx
+    # nothing of the roots is written
+    belief1, history1, pob1 = roots_of(e, hist)
+    assert np.array_equal(u32(e.state).reshape(o.words, R), state0) and np.array_equal(pob1, pob)
+    for k in history:
+        assert np.array_equal(history1[k], history[k]), k
+    if belief is not None:
+        for k in belief:
+            assert belief1[k].tobytes() == belief[k].tobytes(), k
+    if b is not None:
+        assert np.array_equal(u32(columns_of(e, b)), states)
+    return dict(want["stats"], plan=want_plan, sims=want)
 
 
 @pytest.mark.parametrize("shape", range(len(SHAPES)), ids=SHAPE_IDS)
@@ -223,3 +321,203 @@ def test_refusals():
     t = e.call_counter
     e.plan(4, 8, policy="preferred", history=hist)                       # and the accepted form runs
     assert e.call_counter == t + 4
+
+
+# ---- constructed roots (rr.construct_roots): every policy branch, every env parameter, every launch shape ---------------------
+# The restatement's CPU time per case (measured on the host, counters included): 0.2 - 0.4 s for the RockSample envs, 0.1 - 0.15 s
+# for Tag at 96 x 64 x 24, from true states or from 4 particles; all twenty cases together 5 s.
+@pytest.mark.parametrize("P", [1, 4], ids=["true", "P4"])
+@pytest.mark.parametrize("case", range(len(CONSTRUCTED)), ids=C_IDS)
+def test_constructed_roots_match_the_restatement(case, P):
+    """96 roots x 64 simulations x 24 steps from roots whose statistics stand at the policy's thresholds, a quarter of them with
+    an empty history: test_preferred_host.py counts, for these very inputs (true states), the simulations that read their
+    own workspace entry back, the legal fallback and its CHECKs of closed rocks, [EAST], [SAMPLE], every crossing of a
+    derived bit in both directions, Tag's corner rule and its five actions from an empty history.  Closed rocks are exact
+    zeros in lkw / lkv that agree with every state column of the root, so no simulation reaches 0 / 0: asserted."""
+    env, kw, prep = CONSTRUCTED[case]
+    o, e, hist, b = constructed(env, kw, C_ROOTS, prep, P)
+    s = check_launch(o, e, hist, b, C_ROOTS, P, C_SIMS, C_DEPTH, 0, None, (C_IDS[case], P))
+    assert s["nan_prob"] == 0
+    assert s["from_empty_history"] >= C_SIMS
+    if rr.is_rock(o):
+        assert s["repeat_check"] >= 1 and s["fallback_check_of_closed"] >= 1 and s["check_ok_set_again"] >= 1, s
+
+
+# The restatement's CPU time at 40 x 64 x 16 (measured on the host): 0.1 s for RockSample, 0.05 s for Tag.
+@pytest.mark.parametrize("env,kw", [("rock", {}), ("tag", {})], ids=["rock7x8", "tag"])
+def test_planning_from_a_fresh_history(env, kw):
+    """reset(), History(env) and plan(policy="preferred") with no step in between — size 0 at every root: Tag lists all five
+    actions, RockSample's SAMPLE rule is off whatever the sums say, and a simulation's size turns 1 after its first step —
+    then plan_step twice against the same sequence made of the separate calls."""
+    import gym_pomdp_amd as gpa
+    from oracle import oracle_lib as ol
+    R, sims, depth = 40, 64, 16
+    o = ol.OracleEnv(env, **kw)
+    envs = []
+    for _ in range(2):
+        e = make(env, kw, R, lane_offset=4)
+        e.reset()
+        envs.append((e, gpa.History(e)))
+    (e1, h1), (e2, h2) = envs
+    assert int(np_(h1._size).max()) == 0
+    s = check_launch(o, e1, h1, None, R, 1, sims, depth, 4, None, (env, "fresh"))
+    assert s["from_empty_history"] == R * sims and s["nan_prob"] == 0
+    assert s["empty_history_all_five"] == R * sims if env == "tag" else len(np.unique(s["sims"]["first_action"])) > 1
+    e1.call_counter = e2.call_counter
+    for step in range(2):
+        ob1, rew1, done1, _, p1 = e1.plan_step(depth, sims, policy="preferred", history=h1)
+        p2 = e2.plan(depth, sims, policy="preferred", history=h2)
+        best = p2["best"].clone()
+        ob2, rew2, done2, _ = e2.step(best)
+        h2.append(gpa.Transition(h2.prev_ob, best, rew2, ob2, done2), auto_reset=False)
+        h2.prev_ob.copy_(ob2)
+        assert np.array_equal(np_(p1["best"]), np_(best)) and np_(p1["q"]).tobytes() == np_(p2["q"]).tobytes()
+        assert np.array_equal(np_(ob1), np_(ob2)) and np.array_equal(np_(done1), np_(done2)) and np.array_equal(np_(rew1), np_(rew2))
+        assert np.array_equal(u32(e1.state), u32(e2.state))
+        a1, a2 = roots_of(e1, h1), roots_of(e2, h2)
+        assert np.array_equal(a1[2], a2[2]) and np.array_equal(a1[2], np_(ob1))
+        for k in a1[1]:
+            assert np.array_equal(a1[1][k], a2[1][k]), k
+        if a1[0] is not None:
+            for k in a1[0]:
+                assert a1[0][k].tobytes() == a2[0][k].tobytes(), k
+    assert int(np_(h1._size).max()) == 2
+
+
+# (roots, simulations per root, depth, particles, lane_offset, call counter or None).  The step loop is unrolled by four with a
+# step guard (depths 0, 1, 2, 3, 5, 7), a quad of simulations spans up to four roots' policy words (1, 2, 3 simulations per
+# root), threads past n take part in the quad's transposes (n % 4 of 1 and 3, n = 1, three live threads in the last block).
+# 37 x 7 x 31 is the same ragged launch past its fourth step: the block of step base + 3 comes from the quad's padding thread.
+# The restatement takes under 0.1 s at each but the last two (0.1 s and 0.3 s for RockSample).
+# These launches, the last lanes, the workspace runs and the shards assert the comparison and nan_prob == 0 only: a launch
+# of a few simulations reaches few of the policy's branches, and the 96 x 64 x 24 grids above carry the branch coverage that
+# test_preferred_host.py counts.
+EDGES = [(1, 1, 5, 1, 4, None),
+         (5, 1, 7, 1, 8, None),
+         (37, 7, 3, 1, 4, None),                                        # n = 259: one block and three threads, n % 4 == 3
+         (37, 7, 31, 1, 4, None),
+         (37, 3, 2, 3, 4, None),                                        # one simulation per particle column (C ABI only)
+         (9, 2, 1, 1, 8, None),
+         (64, 4, 0, 1, 12, None),                                       # depth 0
+         (33, 12, 5, 4, 4, (1 << 32) + 7),                              # the call counter past 2^32
+         (3, 256, 32, 1, 8, None)]                                      # whole blocks, three roots
+EDGE_IDS = ["1x1x5", "5x1x7", "37x7x3", "37x7x31", "37x3x2-P3", "9x2x1", "64x4x0", "33x12x5-P4-t>2^32", "3x256x32"]
+
+
+@pytest.mark.parametrize("shape", range(len(EDGES)), ids=EDGE_IDS)
+@pytest.mark.parametrize("case", [0, 6], ids=["rock7x8", "tag"])
+def test_shape_edges_from_constructed_roots(case, shape):
+    env, kw, prep = CONSTRUCTED[case]
+    R, sims, depth, P, lane_offset, counter = EDGES[shape]
+    o, e, hist, b = constructed(env, kw, R, prep, P, lane_offset)
+    t = e.call_counter if counter is None else counter
+    s = check_launch(o, e, hist, b, R, P, sims, depth, lane_offset, counter, (C_IDS[case], EDGE_IDS[shape]))
+    assert s["nan_prob"] == 0
+    if depth == 0:                                                      # nothing runs: no return, no action, no visit, no call consumed
+        assert e.call_counter == t
+        got = raw_rollout(e, hist, e._state, R, P, sims, 0, lane_offset * sims, t)
+        assert not np_(got["ret"]).any() and (np_(got["first_action"]) == -1).all() and not np_(got["n_steps"]).any()
+        assert not np_(got["terminated"]).any()
+        p = e.plan(0, sims, policy="preferred", history=hist)
+        assert not np_(p["visits"]).any() and (np_(p["best"]) == -1).all() and e.call_counter == t
+    else:                                                               # (a Tag root may stand next to its episode's end)
+        assert int(s["sims"]["n_steps"].max()) == depth or env == "tag"
+
+
+# The restatement's CPU time at 5 x 12 x 6 (measured on the host): 0.01 s.
+@pytest.mark.parametrize("case", [0, 6], ids=["rock7x8", "tag"])
+def test_c_abi_at_the_last_lanes_and_four_past_them(case):
+    """pomdp_rollout_preferred with lane0 = 2^32 - n: the last simulation is global lane 0xFFFFFFFF.  Four lanes further the call
+    is refused and nothing is launched."""
+    env, kw, prep = CONSTRUCTED[case]
+    from oracle import oracle_lib as ol
+    R, sims, depth = 5, 12, 6
+    n = R * sims
+    lane0 = (1 << 32) - n
+    assert n % 4 == 0 and lane0 % 4 == 0
+    o, e, hist, _ = constructed(env, kw, R, prep)
+    belief, history, pob = roots_of(e, hist)
+    t0 = e.call_counter
+    want = rr.rollout(o, u32(e.state).copy(), belief, history, pob, R, 1, sims, depth, e._discount, e._seed, lane0, t0, nthreads=ol.max_threads())
+    got = raw_rollout(e, hist, e._state, R, 1, sims, depth, lane0, t0)
+    for k in FIVE:
+        assert np.array_equal(np_(got[k]), want[k]), (env, k)
+    assert np_(got["ret"]).tobytes() == want["ret"].tobytes()
+    assert int(want["n_steps"].max()) > 1
+    for k in FIVE:
+        got[k].fill_(-7 if k != "terminated" else 9)
+    raw_rollout(e, hist, e._state, R, 1, sims, depth, lane0 + 4, t0, out=got, refused=True)
+    torch.cuda.synchronize()
+    assert all((np_(got[k]) == (-7 if k != "terminated" else 9)).all() for k in FIVE)
+
+
+# The restatement's CPU time at 33 x 28 x 24 (measured on the host): 0.1 s; the shards below need no restatement.
+def test_workspace_contents_do_not_matter():
+    """The copy-on-first-touch workspace is read only where the simulation wrote it: the same RockSample launch with the
+    workspace zeroed, filled with 0xFF (counts of -1, NaN likelihoods) and left over from a launch from other roots gives the
+    same bytes, the restatement's — whose simulations do read entries back (repeat_check).  plan(out=) with the cached
+    workspace of an earlier call, of the same shape and of a smaller one (it is replaced), equals a fresh call."""
+    from oracle import oracle_lib as ol
+    env, kw, prep = CONSTRUCTED[0]
+    R, sims, depth = 33, 28, 24
+    n = R * sims
+    o, e, hist, _ = constructed(env, kw, R, prep, lane_offset=8)
+    _, e2, hist2, _ = constructed(env, kw, R, prep + 3, lane_offset=8, root_seed=ROOT_SEED + 1)      # other roots
+    belief, history, pob = roots_of(e, hist)
+    t0, lane0 = e.call_counter, 8 * sims
+    want = rr.rollout(o, u32(e.state).copy(), belief, history, pob, R, 1, sims, depth, e._discount, e._seed, lane0, t0, nthreads=ol.max_threads(),
+                      counters=True)
+    assert want["stats"]["repeat_check"] >= n // 4 and want["stats"]["nan_prob"] == 0
+    ws = torch.zeros(32 * e.num_rocks * n, dtype=torch.uint8, device=e.device)
+    runs = [raw_rollout(e, hist, e._state, R, 1, sims, depth, lane0, t0, workspace=ws)]
+    ws.fill_(0xFF)
+    runs.append(raw_rollout(e, hist, e._state, R, 1, sims, depth, lane0, t0, workspace=ws))
+    raw_rollout(e2, hist2, e2._state, R, 1, sims, depth, lane0, e2.call_counter, workspace=ws)
+    runs.append(raw_rollout(e, hist, e._state, R, 1, sims, depth, lane0, t0, workspace=ws))
+    for r in runs:
+        for k in FIVE:
+            assert np.array_equal(np_(r[k]), want[k]), k
+        assert np_(r["ret"]).tobytes() == want["ret"].tobytes()
+    keys = ("q", "visits", "best", "value", "sim_ret", "sim_first_action")
+    small = e.plan(depth, sims, policy="preferred", history=hist)
+    fresh = {k: np_(small[k]).copy() for k in keys}
+    assert fresh["sim_ret"].tobytes() == want["ret"].tobytes()
+    assert small["_workspace"].numel() == 32 * e.num_rocks * n
+    e2.plan(depth, sims, policy="preferred", history=hist2, out=dict(small))          # other roots' entries in the cached workspace
+    e.call_counter = t0
+    again = e.plan(depth, sims, policy="preferred", history=hist, out=small)
+    assert again is small and all(np_(again[k]).tobytes() == fresh[k].tobytes() for k in keys)
+    e.call_counter = t0
+    big = e.plan(depth, 2 * sims, policy="preferred", history=hist)
+    fresh_big = {k: np_(big[k]).copy() for k in keys}
+    big["_workspace"] = small["_workspace"]                             # too small for this shape: _preferred_args replaces it
+    e.call_counter = t0
+    again = e.plan(depth, 2 * sims, policy="preferred", history=hist, out=big)
+    assert again["_workspace"].numel() == 32 * e.num_rocks * 2 * n
+    assert all(np_(again[k]).tobytes() == fresh_big[k].tobytes() for k in keys)
+
+
+def test_constructed_roots_with_particles_planned_in_shards():
+    """Geometry independence as the header states it, where the simulations carry the most: constructed RockSample roots with
+    4 particles each planned whole, and as three shards of whole roots, each an env of its own at its lane_offset."""
+    import gym_pomdp_amd as gpa
+    env, kw, prep = CONSTRUCTED[0]
+    R, sims, depth, P, cuts = 48, 64, 24, 4, (0, 20, 36, 48)
+    o, e, hist, b = constructed(env, kw, R, prep, P)
+    belief, history, pob = roots_of(e, hist)
+    whole = e.plan(depth, sims, policy="preferred", history=hist, belief=b)
+    t0 = e.call_counter - depth
+    parts = []
+    for lo, hi in zip(cuts[:-1], cuts[1:]):
+        s = make(env, kw, hi - lo, lane_offset=lo)
+        ob = s.reset()
+        h = gpa.History(s)
+        sb = s.particle_belief(P)
+        sb.reset(ob)
+        sb.particles.copy_(b.particles[:, lo * P:hi * P])
+        rr.put_roots(s, h, {k: v[:, lo:hi] for k, v in belief.items()}, {k: v[..., lo:hi] for k, v in history.items()}, pob[lo:hi])
+        s.call_counter = t0
+        parts.append(s.plan(depth, sims, policy="preferred", history=h, belief=sb))
+    for k in ("q", "visits", "best", "value", "sim_ret", "sim_first_action"):
+        assert np.concatenate([np_(p[k]) for p in parts]).tobytes() == np_(whole[k]).tobytes(), k
+    assert len(np.unique(np_(whole["best"]))) > 1

@@ -19,6 +19,14 @@ NAMES = ("pomdp_rollout_preferred_workspace", "pomdp_rollout_preferred", "pomdp_
 GPU_CASES = [("rock", {}, 6), ("rock", dict(board_size=15, num_rocks=15), 8), ("stochrock", {}, 6), ("tag", {}, 5)]
 GPU_IDS = ["rock7x8", "rock15x15", "stochrock7x8", "tag"]
 SEED, ROOTS, SIMS, DEPTH = 4242, 96, 1024, 64
+# what test_gpu_preferred.py runs from CONSTRUCTED roots (rr.construct_roots with ROOT_SEED on the roots prepared as above):
+# every env parameter the policy code reads, C_ROOTS roots x C_SIMS simulations x C_DEPTH steps, from the true states and from
+# C_PARTICLES particles per root
+CONSTRUCTED = [("rock", {}, 6), ("rock", dict(board_size=4, num_rocks=3), 3), ("rock", dict(board_size=11, num_rocks=11), 7),
+               ("rock", dict(board_size=15, num_rocks=15), 8), ("stochrock", {}, 6), ("stochrock", dict(p_move=.4), 6),
+               ("tag", {}, 5), ("tag", dict(num_opponents=2), 5), ("tag", dict(num_opponents=4), 5), ("tag", dict(move_prob=.4), 5)]
+C_IDS = ["rock7x8", "rock4x3", "rock11x11", "rock15x15", "stochrock7x8", "stochrock7x8-p.4", "tag", "tag-2opp", "tag-4opp", "tag-move.4"]
+C_ROOTS, C_SIMS, C_DEPTH, C_PARTICLES, ROOT_SEED = 96, 64, 24, 4, 1
 
 
 def test_entry_points_are_declared_exported_and_bound():
@@ -133,3 +141,65 @@ def test_gpu_inputs_are_not_vacuous(case):
         assert r["stats"]["cleared_check_ok"] >= 1
         assert r["stats"]["sample_rule"] >= 1
     assert r["n_steps"].max() == DEPTH and len(np.unique(r["first_action"])) > 1
+
+
+# The restatement's CPU seconds per case at 96 x 64 x 24 with the counters on, true states / 4 particles (the particle
+# filter's own restatement included), measured on the host with 8 threads; a first call adds the threads' start-up:
+#   rock7x8 0.3 / 0.4    rock4x3 0.2 / 0.2    rock11x11 0.2 / 0.3    rock15x15 0.3 / 0.4    stochrock7x8 0.3 / 0.3
+#   stochrock7x8-p.4 0.3 / 0.3    tag, tag-2opp, tag-4opp, tag-move.4 0.1 / 0.15 each            all twenty together 5 s
+@pytest.mark.parametrize("P", [1, C_PARTICLES], ids=["true", "P4"])
+@pytest.mark.parametrize("case", range(len(CONSTRUCTED)), ids=C_IDS)
+def test_constructed_roots_reach_every_policy_branch(case, P, capsys):
+    """The constructed roots test_gpu_preferred.py plans from, at its seeds and shape, from the true states and from the 4
+    particles per root that followed the same steps, rolled out on the restatement.  Every counter of rr.COUNTERS that
+    applies to the env is >= 1.  That holds for all six RockSample cases and includes the legal fallback, its CHECKs of
+    closed rocks and the all-bad [EAST]: the cornered roots of rr.construct_roots reach them on the 11 x 11 and 15 x 15
+    boards too.  No prob_valuable is NaN: a closed rock agrees with every column of its root.  No RockSample root has ended."""
+    from oracle import oracle_lib as ol
+    name, kw, prep = CONSTRUCTED[case]
+    o = ol.OracleEnv(name, **kw)
+    nt = ol.max_threads()
+    got = rr.prepare_roots(o, C_ROOTS, prep, SEED, 0, nthreads=nt, P=P)
+    st, bel, hist, pob, done = got[:5]
+    cols = st if P == 1 else got[5]
+    if rr.is_rock(o):
+        assert not done.any()
+    before = {k: v.copy() for k, v in hist.items()}
+    b2, h2, p2 = rr.construct_roots(o, cols, P, bel, hist, pob, ROOT_SEED)
+    assert all(np.array_equal(hist[k], before[k]) for k in hist)        # copies: the prepared roots are left alone
+    assert (h2["size"] == 0).any() and (h2["size"] > 0).any()
+    assert (h2["last_action"][h2["size"] == 0] == -1).all() and (h2["last_ob"][h2["size"] == 0] == -1).all()
+    if rr.is_rock(o):
+        K = o.n_actions - 5
+        assert {1, 2} <= set(p2.tolist()) and not np.array_equal(h2["total_move"], hist["total_move"])
+        codes = rr.rock_codes(o, cols).reshape(K, C_ROOTS, P)
+        assert (b2["lkw"] == 0).any() and (b2["lkv"] == 0).any()
+        # an exact 0 agrees with the rock's value in every column (1: collected during the prepared steps, never CHECKed again)
+        assert np.isin(codes[b2["lkw"] == 0], (2, 1)).all() and np.isin(codes[b2["lkv"] == 0], (0, 1)).all()
+    r = rr.rollout(o, cols, b2, h2, p2, C_ROOTS, P, C_SIMS, C_DEPTH, .95, SEED, 0, prep + 1, nthreads=nt, counters=True)
+    s = r["stats"]
+    with capsys.disabled():
+        print("\n%s-P%d: %s" % (C_IDS[case], P, ", ".join("%s %d" % (k, s[k]) for k in rr.COUNTERS if s[k] or k == "nan_prob")))
+    assert s["nan_prob"] == 0
+    for k in (rr.ROCK_COUNTERS if rr.is_rock(o) else rr.TAG_COUNTERS):
+        assert s[k] >= 1, (C_IDS[case], P, k, s[k])
+    assert s["from_empty_history"] == int((h2["size"] == 0).sum()) * C_SIMS
+    assert r["n_steps"].max() == C_DEPTH and len(np.unique(r["first_action"])) > 1
+
+
+@pytest.mark.parametrize("name", ["rock", "tag"])
+def test_counters_leave_the_restatement_alone(name):
+    """the counters only read: the five outputs and the old statistics with and without them are the same, from constructed roots"""
+    from oracle import oracle_lib as ol
+    o = ol.OracleEnv(name)
+    st, bel, hist, pob, _ = rr.prepare_roots(o, 24, 6, SEED, 0)
+    bel, hist, pob = rr.construct_roots(o, st, 1, bel, hist, pob, ROOT_SEED)
+    r = rr.rollout(o, st, bel, hist, pob, 24, 1, 16, 12, .95, SEED, 0, 7, counters=True)
+    u = rr.rollout(o, st, bel, hist, pob, 24, 1, 16, 12, .95, SEED, 0, 7)
+    assert set(rr.COUNTERS) | {"cleared_check_ok", "lists0", "lens0"} <= set(r["stats"])
+    for k in ("ret", "n_steps", "first_action", "last_ob", "terminated"):
+        assert r[k].tobytes() == u[k].tobytes(), k
+    for k in ("cleared_check_ok", "sample_rule"):
+        assert r["stats"][k] == u["stats"][k]
+    assert np.array_equal(r["stats"]["lists0"], u["stats"]["lists0"])
+    assert all(u["stats"][k] == 0 for k in rr.COUNTERS if k != "sample_rule") and sum(r["stats"][k] for k in rr.COUNTERS) > 0
