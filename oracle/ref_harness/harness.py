@@ -285,7 +285,9 @@ def trace_mode_b(name, kwargs, seed, lanes, actions, t0=0):
                 max_used = max(max_used, consumed_words())
             out["state"][li, i] = compact_state(name, env)
     assert max_used < N_INJECT, "a reference call consumed more words than were injected"
-    out.update(lanes=np.asarray(lanes, np.int64), actions=actions.astype(np.int64), seed=np.int64(seed),
+    # (a key whose high word has its top bit set does not fit int64: it is recorded as uint64)
+    out.update(lanes=np.asarray(lanes, np.int64), actions=actions.astype(np.int64),
+               seed=np.int64(seed) if seed < 1 << 63 else np.uint64(seed),
                t0=np.int64(t0), max_words_per_call=np.int64(max_used))
     return out
 

@@ -16,6 +16,9 @@ Fixtures:
       live_<id>.npz      modes A and B on seeds drawn once, in configurations
                          of no other fixture (tests/test_reference_live.py;
                          --live-only writes these alone)
+      edge_<env>.npz     mode B at the edges of the Philox key and counter: a
+                         seed with both key words set, lanes up to 0xFFFFFFFF,
+                         a call counter that crosses 2^32 (--key-edges-only)
 """
 import json
 import os
@@ -281,6 +284,35 @@ def gen_live(i, env, kwargs):
     return name, sum(int(out["a%d_done" % j].sum()) for j in range(LIVE_MODE_A[0])), sum(int(out["b%d_done" % j].sum()) for j in range(n_b))
 
 
+# the edges of the Philox key and counter (tests/test_reference_live.py: test_key_and_counter_edges_mode_b; the GPU side is
+# tests/test_gpu_key_edges.py): every base config of LIVE_CASES, one mode-B trace each — both key words non-zero, the last lane
+# 0xFFFFFFFF (counter word 0 all ones; the quad-shared streams' word 0 is 0x3FFFFFFF), t crossing 2^32 at step 7
+EDGE_SEED = 0x9E3779B97F4A7C15
+EDGE_LANES, EDGE_STEPS = 12, 40
+EDGE_LANE0 = (1 << 32) - EDGE_LANES
+EDGE_T0 = (1 << 32) - 7
+EDGE_CASES = [(env, kwargs) for env, kwargs in LIVE_CASES if not kwargs]
+
+
+def gen_key_edge(env, kwargs):
+    nA = n_actions(env, kwargs)
+    tries = 0
+    while True:
+        acts = action_tape(env, nA, np.random.RandomState(0xED6E + tries), (EDGE_LANES, EDGE_STEPS))
+        try:
+            tr = h.trace_mode_b(env, kwargs, EDGE_SEED, range(EDGE_LANE0, EDGE_LANE0 + EDGE_LANES), acts, t0=EDGE_T0)
+            break
+        except IndexError:      # RockSample crash cells
+            tries += 1
+            assert tries < 50
+    out = {"env": np.str_(env), "kwargs": np.str_(json.dumps(kwargs, sort_keys=True)), "seed": np.uint64(EDGE_SEED),
+           "lane0": np.int64(EDGE_LANE0), "t0": np.int64(EDGE_T0), "actions": np.asarray(acts, np.int64)}
+    out.update({k: np.asarray(tr[k]) for k in ("ob0", "ob", "reward", "done", "state")})
+    name = "edge_%s.npz" % env
+    np.savez_compressed(os.path.join(HERE, name), **out)
+    return name, int(out["done"].sum()), int(tr["max_words_per_call"])
+
+
 def gen_thresholds():
     def binom_at(p, k):
         h.inject_words([(k >> 26) << 5, (k & ((1 << 26) - 1)) << 6])
@@ -383,6 +415,11 @@ def main():
         for i, (env, kwargs) in enumerate(LIVE_CASES):
             print("live %-22s modeA dones=%4d  modeB dones=%4d" % gen_live(i, env, kwargs), flush=True)
         return
+    if "--key-edges-only" in sys.argv:
+        for env, kwargs in EDGE_CASES:
+            print("edge %-22s modeB dones=%4d  max words/call=%d" % gen_key_edge(env, kwargs), flush=True)
+        write_manifest()
+        return
     gen_thresholds()
     if "--bounded-history-only" in sys.argv:
         for case, env, kwargs, L, T, ms in HEUR_BOUNDED:
@@ -439,6 +476,8 @@ def main():
     if not only:
         for i, (env, kwargs) in enumerate(LIVE_CASES):
             print("live %-22s modeA dones=%4d  modeB dones=%4d" % gen_live(i, env, kwargs), flush=True)
+        for env, kwargs in EDGE_CASES:
+            print("edge %-22s modeB dones=%4d  max words/call=%d" % gen_key_edge(env, kwargs), flush=True)
     write_manifest()
 
 
@@ -454,6 +493,8 @@ def write_manifest():
                                   for c in PLAN_CASES],
                    "heuristic_cases": [[c[0], c[1], {k: (list(v) if isinstance(v, tuple) else v) for k, v in c[2].items()}]
                                        for c in HEUR_CASES + HEUR_BOUNDED],
+                   "key_edge_cases": [["edge_%s" % env, env, kwargs] for env, kwargs in EDGE_CASES],
+                   "key_edge": {"seed": EDGE_SEED, "lane0": EDGE_LANE0, "lanes": EDGE_LANES, "t0": EDGE_T0, "steps": EDGE_STEPS},
                    "mode_a_seeds": MODE_A_SEEDS, "mode_b_seed": MODE_B_SEED,
                    "numpy": np.__version__}, f, indent=1)
 

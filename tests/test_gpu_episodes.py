@@ -38,18 +38,19 @@ def f64_reward(env, code):
 class Pair(object):
     """the GPU env (auto_reset=False) and the oracle on the same lanes, stepped into a state where some lanes are done"""
 
-    def __init__(self, ol, env, kw, n, lane0, pre_steps=6, seed=SEED, force_done=0.25):
+    def __init__(self, ol, env, kw, n, lane0, pre_steps=6, seed=SEED, force_done=0.25, t0=0):
         self.ol, self.env, self.kw, self.n, self.lane0, self.seed = ol, env, kw, n, lane0, seed
         self.nt = ol.max_threads()
         self.o = ol.OracleEnv(env, **kw)
         self.e = make_env(env, kw, batch_size=n, seed=seed, lane_offset=lane0, auto_reset=False)
+        self.e.call_counter = t0                                       # reset() is call t0
         self.st = self.o.new_state(n)
-        ob = self.o.batch_reset(self.st, seed, lane0, 0, nthreads=self.nt)
+        ob = self.o.batch_reset(self.st, seed, lane0, t0, nthreads=self.nt)
         assert np.array_equal(np_(self.e.reset()), ob)
         self.done = np.zeros(n, np.uint8)
         for _ in range(pre_steps):
             self.step_both()
-        rng = np.random.RandomState(n + lane0)
+        rng = np.random.RandomState((n + lane0) & 0xFFFFFFFF)
         forced = (rng.rand(n) < force_done).astype(np.uint8)           # frozen lanes whatever their state: `done` is an input flag
         self.done |= forced
         self.e._done.copy_(torch.as_tensor(self.done, device=self.e.device))

@@ -498,7 +498,7 @@ def test_bound_argument_entry_points_equal_the_plain_ones():
             assert all(torch.equal(x, y) for x, y in zip(ra[:3], rb[:3])) and torch.equal(a.state, b.state), env
 
 
-def _heuristic_fused_vs_oracle(oracle_lib, env, kw, n, ks, seed, lane0, max_size=None, auto=True, preset=None):
+def _heuristic_fused_vs_oracle(oracle_lib, env, kw, n, ks, seed, lane0, max_size=None, auto=True, preset=None, t0=0):
     """The launches `bench.py --mode heuristic` times — heuristic_steps_kernel, up to 64 steps each — against the oracle's
     lane-major restatement of the reference's rollout loop (rock.py:557-573; or_batch_heuristic_steps, pinned on CPU to the
     per-step batch functions the heur_* fixtures pin to the reference): after every launch the outputs it leaves (the LAST
@@ -512,13 +512,14 @@ def _heuristic_fused_vs_oracle(oracle_lib, env, kw, n, ks, seed, lane0, max_size
     e = make_env(env, dict(kw, **(dict(use_heuristic=True) if is_rock else {})), batch_size=n, seed=seed, lane_offset=lane0,
                  auto_reset=auto, reuse_buffers=True)
     st = o.new_state(n)
-    prev = o.batch_reset(st, seed, lane0, 0, nthreads=nt).astype(np.int32)
+    e.call_counter = t0                                                  # reset() is call t0, the first step call t0 + 1
+    prev = o.batch_reset(st, seed, lane0, t0, nthreads=nt).astype(np.int32)
     assert np.array_equal(np_(e.reset()), prev)
     h = History(e, max_size=max_size)
     b = ol.Belief(o, n) if is_rock else None
     hs = ol.HistorySums(o, n, max_size=max_size)
     frozen = np.zeros(n, np.uint8)
-    t, n_done = 1, 0
+    t, n_done = t0 + 1, 0
     if preset is not None:
         preset(e, h, b, hs)
     for k in ks:

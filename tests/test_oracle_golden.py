@@ -121,6 +121,47 @@ def test_synthetic_actions_agree(oracle_lib):
         assert a.min() >= 0 and a.max() < nA
 
 
+EDGE_KEYS = [1 << 32, (1 << 64) - 1, 0x9E3779B97F4A7C15]
+# (lane word, t): the top lane and the top quad index (lane >> 2 of the quad-shared streams); t on either side of 2^32; t_hi at
+# the top of its range, carrying and carried
+EDGE_COUNTERS = [(lane, t) for lane in (0xFFFFFFFF, 0x3FFFFFFF)
+                 for t in ((1 << 32) - 1, 1 << 32, (1 << 32) + 1, 0xFFFFFFFEFFFFFFFF, 0xFFFFFFFF00000000, 0xFFFFFFFFFFFFFFFF)]
+
+
+@pytest.mark.parametrize("seed", EDGE_KEYS, ids=["k0-zero", "all-ones", "golden-ratio"])
+def test_philox_at_the_edges_of_key_and_counter(oracle_lib, seed):
+    """or_philox4x32_10 == the pure-Python statement of the generator where no other test puts it: keys whose high word is set
+    (k0 = 0 with k1 = 1; all ones; both words mixed) at counters whose lane word is 0xFFFFFFFF / 0x3FFFFFFF, whose t straddles
+    2^32 and whose t_hi is 0xFFFFFFFE / 0xFFFFFFFF, for every stream id and the first blocks."""
+    from oracle import philox_ref as px
+    key = (seed & 0xFFFFFFFF, seed >> 32)
+    assert key[1] != 0
+    for lane, t in EDGE_COUNTERS:
+        for stream in range(9):
+            for block in (0, 1, 5):
+                ctr = (lane, t & 0xFFFFFFFF, t >> 32, stream << 24 | block)
+                want = px.philox4x32_10(np.array(ctr), np.array(key))
+                assert np.array_equal(oracle_lib.philox(ctr, key), want), (hex(seed), ctr)
+                assert np.array_equal(px._block(seed, lane, t, stream, block), want)
+        # dropping the key's high word, or the counter's, gives other words: the comparison above can tell
+        assert not np.array_equal(px._block(seed, lane, t, 0, 0), px._block(seed & 0xFFFFFFFF, lane, t, 0, 0))
+        assert t < 1 << 32 or not np.array_equal(px._block(seed, lane, t, 0, 0), px._block(seed, lane, t & 0xFFFFFFFF, 0, 0))
+
+
+@pytest.mark.parametrize("seed", EDGE_KEYS, ids=["k0-zero", "all-ones", "golden-ratio"])
+def test_synthetic_actions_at_the_edges_of_key_and_counter(oracle_lib, seed):
+    """or_synthetic_actions == philox_ref.synthetic_actions at the same keys: the last 64 lanes below 2^32 (quad index up to
+    0x3FFFFFFF) and a ragged range that ends at lane 0xFFFFFFFF, at call counters on either side of 2^32, with t_hi =
+    0xFFFFFFFE / 0xFFFFFFFF, and at t = 0."""
+    from oracle import philox_ref as px
+    for lane0, n in (((1 << 32) - 64, 64), ((1 << 32) - 12, 12), ((1 << 32) - 1028 + 1, 1027), (1 << 22, 257), (0, 64)):
+        for t in (0, (1 << 32) - 1, 1 << 32, (1 << 32) + 1, 0xFFFFFFFEFFFFFFFF, 0xFFFFFFFF00000000, 0xFFFFFFFF00000014):
+            for nA in (13, 3, 100):
+                a = oracle_lib.synthetic_actions(n, seed, lane0, t, nA, nthreads=2)
+                assert np.array_equal(a, px.synthetic_actions(seed, lane0, n, t, nA)), (hex(seed), lane0, n, t, nA)
+                assert a.min() >= 0 and a.max() < nA
+
+
 def test_oracle_threads_agree(oracle_lib):
     o = oracle_lib.OracleEnv("rock")
     n = 5000
