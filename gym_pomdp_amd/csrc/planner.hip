@@ -140,6 +140,9 @@ static __device__ __forceinline__ void history_check_sums(const pomdp_history &h
 // max_size + 1 rows, `head` = the row the next transition goes to, which holds the OLDEST one once the ring is full:
 // the reference pops element 0 when size > max_size and then appends, so the list settles at max_size + 1 records) and,
 // for RockSample (K > 0), the two per-rock sums kept current as transitions enter and leave the window.
+// A record leaves the sums with exactly what it entered them with ONLY for what the byte holds — an action in [0, 31] and a
+// next observation in [0, 3]: the caller hands in nothing else (the heuristic loop's come from the env; history_append_kernel
+// canonicalises the caller's int32s first).
 // RING = false: the caller knows there is no window to keep (an unbounded history, or an env without rocks) — the
 // heuristic loop is instantiated both ways so that the unbounded history does not carry the window's registers and branches.
 template <bool RING = true>
@@ -187,9 +190,12 @@ __global__ __launch_bounds__(BLOCK) void history_append_kernel(pomdp_history h, 
         return;
     }
     const int a = action[i], o = next_observation[i];
+    // append() takes any int32 (37 & 31 is CHECK 0; 4 << 5 is the BAD bit): the window keeps what the sums take from the
+    // record — an action that is no action of this env as a non-CHECK (31), a next observation that is no CHECK result as 0
+    const int wa = (a >= 0 && a < 5 + K) ? a : 31, wo = (o == 1 || o == 2) ? o : 0;
     int hsize = h.size[i], head = h.head ? h.head[i] : 0;
     uint32_t mv = K ? h.move_ok[i] : 0u;
-    history_push(h, K, a, o, observation[i], n, (uint32_t)i, hsize, head, mv);
+    history_push(h, K, wa, wo, observation[i], n, (uint32_t)i, hsize, head, mv);
     h.size[i] = hsize; h.last_action[i] = a; h.last_ob[i] = o;
     if (K) h.move_ok[i] = mv;
     if (h.head) h.head[i] = head;

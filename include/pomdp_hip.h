@@ -515,7 +515,9 @@ typedef struct pomdp_plan_out {
     int32_t  reserved;
 } pomdp_plan_out;
 /* the reduction alone, over per-simulation returns / first actions the caller already has (n_actions <= 255; a
- * first_action outside [0, n_actions) — pomdp_rollout's -1 — counts for no action) */
+ * first_action outside [0, n_actions) — pomdp_rollout's -1 — counts for no action).  Non-finite returns go through the same
+ * additions (+inf and -inf on one action: q = NaN), and `best` compares with >, which is false for NaN either way: a NaN q is
+ * taken only as the first visited action, and then stays. */
 int pomdp_plan_reduce(const double *ret, const int32_t *first_action, int64_t n_roots, int64_t sims_per_root,
                       int n_actions, const pomdp_plan_out *out, void *stream);
 /* pomdp_rollout (same arguments, same lanes, same draws) followed by pomdp_plan_reduce: two launches.  sim_ret /
@@ -634,7 +636,10 @@ typedef struct pomdp_history {
 int pomdp_history_clear(int env, const void *params, const pomdp_history *h, const uint8_t *where, int64_t n,
                         void *stream);
 /* history.append(Transition(observation, action, reward, next_observation, done)) per lane (rock.py:541-544).  With
- * POMDP_AUTO_RESET a done transition ends the episode and the lane's history starts over, empty. */
+ * POMDP_AUTO_RESET a done transition ends the episode and the lane's history starts over, empty.
+ * Any int32 is taken: last_action / last_ob keep the caller's values, while a bounded RockSample window keeps a record as
+ * what the two sums take from it — an action outside [0, 5 + num_rocks) as a non-CHECK (31), a next observation other than
+ * 1 or 2 as 0 — so that a record leaves the sums with exactly what it entered them with. */
 int pomdp_history_append(int env, const void *params, const pomdp_history *h, const int32_t *observation,
                          const int32_t *action, const int32_t *next_observation, const uint8_t *done, int64_t n,
                          int flags, void *stream);

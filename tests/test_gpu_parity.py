@@ -939,6 +939,7 @@ def test_network_split_layout_ties():
 
 # ---- heuristic policy support -----------------------------------------------------------
 from conftest import OracleHeuristicOps, golden_manifest, heuristic_replay  # noqa: E402
+from history_window_restatement import window_sums  # noqa: E402
 
 HEUR = [tuple(c) for c in golden_manifest().get("heuristic_cases", [])]
 
@@ -1048,9 +1049,10 @@ def test_heuristic_vs_oracle_at_scale(env, kw, n, T, max_size):
             for k in bc:
                 same = (bc[k] == bg[k]) | ((bc[k] != bc[k]) & (bg[k] != bg[k]))
                 assert same.all(), (t, k)
-        # (a bounded history's sums: the oracle walks its records when asked, so only the HIP side keeps them as arrays)
-        for k in ("size", "last_action", "last_ob") + (("total_sample", "total_move") if max_size is None else ()):
-            assert np.array_equal(getattr(cpu.h, k), np_(getattr(gpu.h, "_size" if k == "size" else k))), (t, k)
+        # (a bounded history's sums: the oracle walks its records when asked — window_sums is that walk, as arrays)
+        ws = dict(zip(("total_sample", "total_move"), window_sums(cpu.h, o.n_actions - 5))) if is_rock and max_size is not None else {}
+        for k in ("size", "last_action", "last_ob") + (("total_sample", "total_move") if max_size is None or is_rock else ()):
+            assert np.array_equal(ws.get(k, getattr(cpu.h, k)), np_(getattr(gpu.h, "_size" if k == "size" else k))), (t, k)
         if max_size is not None:
             assert int(cpu.h.size.max()) <= max_size + 1
         if is_rock:      # the derived words the policy reads == the per-rock tests on the oracle's full arrays
@@ -1059,7 +1061,7 @@ def test_heuristic_vs_oracle_at_scale(env, kw, n, T, max_size):
             ok = (bc["measured"] < 5) & (np.abs(bc["count"]) < 2) & (bc["prob_valuable"] > 0) & (bc["prob_valuable"] < 1)
             assert np.array_equal((ok * w).sum(axis=0), np_(gpu.e._tracker.check_ok).astype(np.int64) & 0xFFFFFFFF), t
             mo = np_(gpu.h.move_ok).astype(np.int64) & 0xFFFFFFFF        # bit j: total_move[j] >= 0, bit 16 + j: total_sample[j] > 0
-            tm, ts = (cpu.h.total_move, cpu.h.total_sample) if max_size is None else (np_(gpu.h.total_move), np_(gpu.h.total_sample))
+            tm, ts = ws.get("total_move", cpu.h.total_move), ws.get("total_sample", cpu.h.total_sample)
             assert np.array_equal(((tm >= 0) * w).sum(axis=0), mo & 0xFFFF), t
             assert np.array_equal(((ts > 0) * w).sum(axis=0), mo >> 16), t
     # (a policy that forgets its old CHECKs keeps re-measuring: with a short window no episode need end inside T steps)

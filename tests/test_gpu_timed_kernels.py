@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+import history_window_restatement as hw
 from conftest import REPO
 from test_gpu_parity import make_env, np_
 
@@ -535,9 +536,11 @@ def _heuristic_fused_vs_oracle(oracle_lib, env, kw, n, ks, seed, lane0, max_size
             frozen = want["done"][-1].copy()
         live = frozen == 0
         assert np.array_equal(np_(h.prev_ob)[live], prev[live]), ctx
-        for name in ("size", "last_action", "last_ob") + (("total_sample", "total_move") if is_rock and max_size is None else ()):
+        # a bounded history's sums are its window's: the oracle keeps the records (rock.py:533-544) and walks them
+        ws = dict(zip(("total_sample", "total_move"), hw.window_sums(hs, o.n_actions - 5))) if is_rock and max_size is not None else {}
+        for name in ("size", "last_action", "last_ob") + (("total_sample", "total_move") if is_rock else ()):
             got = np_(getattr(h, "_size" if name == "size" else name))
-            assert np.array_equal(got[..., live], getattr(hs, name)[..., live]), ctx + (name,)
+            assert np.array_equal(got[..., live], ws.get(name, getattr(hs, name))[..., live]), ctx + (name,)
         if is_rock:
             gb = {k_: np_(v) for k_, v in e.belief.items()}
             for k_, _ in ol.Belief.FIELDS:
@@ -548,10 +551,17 @@ def _heuristic_fused_vs_oracle(oracle_lib, env, kw, n, ks, seed, lane0, max_size
             w = (1 << np.arange(K, dtype=np.int64))[:, None]
             ok = (b.measured < 5) & (np.abs(b.count) < 2) & (b.prob_valuable > 0) & (b.prob_valuable < 1)
             assert np.array_equal((ok * w).sum(axis=0), np_(e._tracker.check_ok).astype(np.int64) & 0xFFFFFFFF), ctx
-            if max_size is None:
-                mo = np_(h.move_ok).astype(np.int64) & 0xFFFFFFFF
-                assert np.array_equal(((hs.total_move >= 0) * w).sum(axis=0), mo & 0xFFFF), ctx
-                assert np.array_equal(((hs.total_sample > 0) * w).sum(axis=0), mo >> 16), ctx
+            mo = np_(h.move_ok).astype(np.int64) & 0xFFFFFFFF
+            tm, ts = ws.get("total_move", hs.total_move), ws.get("total_sample", hs.total_sample)
+            assert np.array_equal(((tm >= 0) * w).sum(axis=0), mo & 0xFFFF), ctx
+            assert np.array_equal(((ts > 0) * w).sum(axis=0), mo >> 16), ctx
+            if max_size is not None:                                     # the ring read back as records == the oracle's records
+                W = max_size + 1
+                win = hw.decode_ring(np_(h.ring), np_(h.head), np_(h._size), W)
+                v = (np.arange(W)[:, None] < hs.size[None, :]) & live[None, :]
+                assert np.array_equal(win["valid"][:, live], (np.arange(W)[:, None] < hs.size[None, :])[:, live]), ctx
+                for name, rec in (("action", hs.rec[1]), ("next", hs.rec[2]), ("bad", hs.rec[0] == 1)):
+                    assert np.array_equal(win[name][v], rec[v]), ctx + ("ring", name)
         n_done += int(want["done"].sum())
     return n_done
 
@@ -568,12 +578,15 @@ def test_heuristic_steps_fused_vs_oracle(oracle_lib, env, kw):
                                                     ("rock", dict(board_size=15, num_rocks=15), 2048 + 3, None, True),
                                                     ("tag", {}, 4096 + 3, None, True), ("stochrock", {}, 1024 + 1, None, False),
                                                     ("tiger", {}, 259, None, True), ("battleship", {}, 1021, None, True),
-                                                    ("rock", {}, 2048, 80, True)],
-                         ids=["rock+1", "rock+2-hist6", "rock15+3", "tag+3", "stochrock+1-frozen", "tiger+3", "battleship+1", "rock-hist80"])
+                                                    ("rock", {}, 2048, 80, True), ("rock", {}, 4096 + 2, 0, True),
+                                                    ("rock", {}, 4096 + 2, 1, True), ("rock", {}, 4096 + 2, 3, True)],
+                         ids=["rock+1", "rock+2-hist6", "rock15+3", "tag+3", "stochrock+1-frozen", "tiger+3", "battleship+1", "rock-hist80",
+                              "rock+2-hist0", "rock+2-hist1", "rock+2-hist3"])
 def test_heuristic_multi_step_launches_on_ragged_batches_vs_oracle(oracle_lib, env, kw, n, max_size, auto):
     """n % 4 != 0 with several steps per launch: the padding threads of the last quad take part in the quad transposes that
     hand the policy's (and RockSample's sensor) blocks of steps base + 1 .. 3 to the quad's in-range lanes, so their lane
-    ids must be the unclamped ones (round 3's advisor finding: they used lane n - 1's)."""
+    ids must be the unclamped ones (round 3's advisor finding: they used lane n - 1's).  hist0 / hist1 / hist3: windows
+    shorter than the step loop's unroll of four, carried in registers across the launch."""
     _heuristic_fused_vs_oracle(oracle_lib, env, kw, n, (64, 5, 64, 2), seed=4242, lane0=1 << 10, max_size=max_size, auto=auto)
 
 
