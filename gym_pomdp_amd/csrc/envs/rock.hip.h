@@ -454,8 +454,9 @@ struct RockEnv {
     // lookup per lane-step.  With 4-byte trajectory records the fused loops are bound by instruction issue; a lane step that
     // fills (reward, done, aux) for a separate sensor / select stage cost ~49 vector instructions (round 3's step_tab, gone
     // since every table-driven launch takes this form).  step_rec produces the lane's Packed record
-    // (traj_out.hip.h: action | ob << 8 | reward code << 16 | done << 24) and its new state in ~31, from a table whose
-    // entries already hold, per (action, position), everything that does not depend on the rocks' codes:
+    // (traj_out.hip.h: action | ob << 8 | reward code << 16 | done << 24) and its new state in 20 with one state word (measured
+    // in the quad loop's gfx950 code; 27 until the entry held the record's bytes), from a table whose entries already hold, per
+    // (action, position), everything that does not depend on the rocks' codes:
     //   every entry: bits 28-30 = the OUTCOME CODE the step has when no uncollected rock is sampled ("fallback"), bit 31 =
     //                a rock with an id < K lies under a SAMPLE;
     //   a <  4: bits 0-7 = position byte XOR new position byte (0 if the move leaves); fallback 6 inside, 3 leaving east,
@@ -468,18 +469,30 @@ struct RockEnv {
     //   a <  5: bit 27 set.  (H >> 5) | 6 << 28 has bit 27 clear, so only a CHECK's entry can tie with it: the tie test needs
     //           no test of the action.
     // Outcome codes: 0 = bad rock sampled (-10), 1 = penalty (-100, done), 2 = good rock sampled (+10), 3 = east exit (+10,
-    // done), 6 = nothing (0) — a sampled rock's own code IS its outcome code, done is bit 0, and the reward byte is one
-    // v_perm_b32 lookup in an 8-byte constant.
+    // done), 6 = nothing (0) — a sampled rock's own code IS its outcome code, done is bit 0.
     // One state word (K <= 12): the entry is 8 bytes, read with one ds_read_b64 (17 x 256 x 8 = 34 KB of LDS per workgroup,
-    // four workgroups per CU fit).  The second word holds what the first leaves to tests of the action:
-    //   bits 16-23 = a move's position delta (the first word's low byte; 0 in every other entry, so it is XORed in unselected);
-    //   a >= 5: bits 0-4 = the bit offset 2 a - 1 of the CHECKed rock's upper code bit ("good"), bits 8-9 = 3; every other
-    //           entry 0 — the observation is (bits 8-9) & (2 << 8 if the reading matches the rock, else 1 << 8), zero unless
-    //           a CHECK.
-    // Two state words keep 4-byte entries (21 x 256 x 8 = 42 KB would leave three workgroups per CU) and test the action.
-    static constexpr uint32_t REC_LUT_LO = 0x0A0A9CF6u, REC_LUT_HI = 0x00000000u;   // reward byte by outcome code 0..7
+    // four workgroups per CU fit).  The second word is the fallback's record in its final place, and where the state changes:
+    //   bits 16-23 = the fallback's reward byte, bit 24 = its done bit: the record's upper half as it is stored;
+    //   bits 8-9   = 3 in a CHECK's entry, else 0: the record's ob field keeps bit 9 if the reading matches the rock, else
+    //                bit 8 (one select between two masks, one v_and_or_b32 that also puts the action in);
+    //   bits 0-4   = a bit offset `off` into the state word, bits 5-6 = a signed step c in {-1, 0, +1}: the new state is
+    //                s + (c << off).  A move: off = 0 (x) or 4 (y), c = the direction, 0 if it leaves (no carry leaves the
+    //                nibble of a move that stays inside).  SAMPLE and CHECK: off = where the code of the rock underfoot / of the
+    //                measured rock lies, c = 0 — one v_bfe_u32 reads that code q for both: a CHECK's rock is good iff q == 2; a
+    //                SAMPLE with a rock underfoot and q != 1 collects it, code -> 1, which is the step c = 1 - q at the same
+    //                offset, and its record is 0x00F60004 - q * 0x00760000 (reward byte 0xF6 = -10 or 0x0A = +10, action 4).
+    // done is read off the finished record (>= 1 << 24).
+    // Two state words keep 4-byte entries (21 x 256 x 8 = 42 KB would leave three workgroups per CU), test the action, and
+    // look the reward byte up by outcome code with one v_perm_b32 in an 8-byte constant; that branch is as it was.
+    static constexpr uint32_t REC_LUT_LO = 0x0A0A9CF6u, REC_LUT_HI = 0x00000000u;   // reward byte by outcome code 0..7 (two state words)
     using TabEntry = typename std::conditional<W == 1, uint2, uint32_t>::type;
     struct RecTab { TabEntry e[TAB_ACTIONS][256]; };
+    // second word of a one-state-word entry: step `c` (-1, 0, +1) at bit offset `off`, ob mask, the record's reward byte and done bit
+    static __device__ __forceinline__ uint32_t rec_f(uint32_t off, int c, uint32_t ob_mask, uint32_t oc)
+    {
+        const uint32_t rbyte = (((uint64_t)REC_LUT_HI << 32 | REC_LUT_LO) >> (8u * oc)) & 0xFFu;
+        return off | (((uint32_t)c & 3u) << 5) | (ob_mask << 8) | (rbyte << 16) | ((oc & 1u) << 24);
+    }
     static __device__ __forceinline__ void build_rec_tab(RecTab &tab, const Shared &sh, const Params &p, int pos)
     {
         const uint32_t x = (uint32_t)pos & 15u, y = (uint32_t)pos >> 4, size = (uint32_t)p.size, K = (uint32_t)p.num_rocks;
@@ -487,19 +500,21 @@ struct RockEnv {
         const uint32_t NOTHING = 6u << 28, PENALTY = (STOCH ? 6u : 1u) << 28, EXIT_EAST = 3u << 28;
         const uint32_t NO_TIE = 1u << 27;
         for (int a = 0; a < 5 + (int)K && a < TAB_ACTIONS; ++a) {
-            uint32_t e, f = 0u;
+            uint32_t e, f;
             if (a < 4) {
                 const uint32_t nx = x + (uint32_t)((a == 1) - (a == 3)), ny = y + (uint32_t)((a == 0) - (a == 2));
                 const bool inside = max(nx, ny) < size;
                 e = inside ? (((uint32_t)pos ^ (nx | (ny << 4))) | NOTHING) : (a == 1 ? EXIT_EAST : PENALTY);
                 e |= NO_TIE;
-                f = (e & 0xFFu) << 16;
+                // x +- 1 is the state word +- 1, y +- 1 is +- 1 << 4 (no carry leaves the nibble of a move that stays inside)
+                f = rec_f((a & 1) ? 0u : 4u, inside ? (a < 2 ? 1 : -1) : 0, 0u, e >> 28 & 7u);
             } else if (a == 4) {
                 const bool rock = (uint32_t)id < K;
                 e = (rock ? ((8u + 2u * (uint32_t)id) | 0x80000000u) : 0u) | PENALTY | NO_TIE;
+                f = rec_f(rock ? 8u + 2u * (uint32_t)id : 0u, 0, 0u, e >> 28 & 7u);
             } else {
                 e = sh.thr[__builtin_amdgcn_sad_u8(x | (y << 8), sh.rpos[a - 5], 0u) & 31u].x | NOTHING;
-                f = (2u * (uint32_t)a - 1u) | (3u << 8);
+                f = rec_f(2u * (uint32_t)a - 2u, 0, 3u, 6u);
             }
             if constexpr (W == 1) tab.e[a][pos] = make_uint2(e, f);
             else tab.e[a][pos] = e;
@@ -517,23 +532,24 @@ struct RockEnv {
         if constexpr (W == 1) {
             const uint2 ef = tab.e[a][s_lo & 0xFFu];
             const uint32_t e = ef.x, f = ef.y;
-            // SAMPLE (rock.py:160-169): the cell's rock code, read at the entry's offset (entries of the other classes: the
-            // sign bit is clear, so whatever this reads is never used)
-            const uint32_t code = __builtin_amdgcn_ubfe(s_lo, e, 2u);
-            const bool ok = ((int32_t)e < 0) & (code != 1u);                    // an uncollected rock with an id < K is underfoot
-            const uint32_t collect = (code ^ 1u) << (e & 31u);                  // its code -> 1
-            const uint32_t d = ok ? collect : __builtin_amdgcn_ubfe(f, 16u, 8u); // ... or a move's position delta (0 for the rest)
-            const uint32_t oc = ok ? code : __builtin_amdgcn_ubfe(e, 28u, 3u);  // outcome code
-            const uint32_t rbyte = __builtin_amdgcn_perm(REC_LUT_HI, REC_LUT_LO, (oc << 16) | 0x0C000C0Cu);   // reward byte << 16
-            const uint32_t done = oc & 1u;
-            // CHECK rock a - 5 (rock.py:171-175, 401-407): good = its upper code bit, at the entry's offset 2a-1
-            const bool good = __builtin_amdgcn_ubfe(s_lo, f, 1u) != 0u;
+            // the code of the rock this step is about — under a SAMPLE, or the one a CHECK measures — read at the entry's offset
+            // (a move's entry points at the position nibble it changes: whatever this reads there is not used)
+            const uint32_t q = __builtin_amdgcn_ubfe(s_lo, f, 2u);
+            const bool ok = ((int32_t)e < 0) & (q != 1u);                       // SAMPLE: an uncollected rock with an id < K is underfoot
+            // CHECK rock a - 5 (rock.py:171-175, 401-407): good = its code is 2
             const uint32_t kh = __builtin_amdgcn_alignbit(12u, H, 5u);          // (H >> 5) | 6 << 28: compares with the entry itself
             bool correct = kh < e;
             if (kh == e) correct = (lo() >> 6) <= thr_lo_of(sh, State{s}, (int)a - 5);   // a CHECK only (NO_TIE); probability 2^-27
-            const uint32_t ob = f & ((good == correct) ? 2u << 8 : 1u << 8);    // 0 unless a CHECK
-            rec = rbyte | (done << 24) | ob | a;
-            s = done ? fresh : (S)(s_lo ^ d);
+            // the record when no live rock is sampled: the entry's own bytes, of its two ob bits the one the reading gives
+            const uint32_t keep = ((q == 2u) == correct) ? 0xFFFFFE00u : 0xFFFFFD00u;
+            const uint32_t rfb = (f & keep) | a;
+            // a sampled rock's code IS its outcome: 0 -> -10 (0xF6), 2 -> +10 (0x0A), never done; the action byte is SAMPLE's
+            const uint32_t rok = 0x00F60004u - q * 0x00760000u;
+            rec = ok ? rok : rfb;
+            // the state moves by a step of -1, 0 or +1 at the entry's offset: a move's nibble, or a sampled rock's code -> 1
+            const int c = ok ? 1 - (int)q : __builtin_amdgcn_sbfe((int)f, 5u, 2u);
+            const uint32_t moved = s_lo + ((uint32_t)c << (f & 31u));
+            s = rec >= (1u << 24) ? fresh : (S)moved;                           // done: byte 3 of the finished record
         } else {
             const uint32_t e = tab.e[a][s_lo & 0xFFu];
             // SAMPLE (rock.py:160-169): the cell's rock code, read at the entry's offset (entries of the other classes: the

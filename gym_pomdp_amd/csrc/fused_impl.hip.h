@@ -375,7 +375,7 @@ __global__ __launch_bounds__(BLOCK) void steps_quad_kernel(uint32_t *__restrict_
     constexpr int W = Env::WORDS;
     using S = typename Env::S;
     __shared__ typename Env::Shared sh;
-    // the lane step yields the lane's packed record straight from RecTab (RockEnv::step_rec, ~31 vector instructions per
+    // the lane step yields the lane's packed record straight from RecTab (RockEnv::step_rec, 20 vector instructions per
     // lane-step with one state word)
     __shared__ typename Env::RecTab tab;
     const uint32_t n_act = (uint32_t)Env::n_actions(p);

@@ -6,7 +6,8 @@
 # usage: tools/gpu_pmc_valu.sh <tag> [sets]    -> gpurun_out/<tag>/{pmc_valu.json, pmc_valu.txt}
 #   sets (default "planners headline envs"): planners = rollouts + heuristic loops; headline = RockSample(7,8) in every sink
 #   (packed, columns, blocked, narrow, returns) x (256, 20) steps per launch + HBM byte passes; envs = the other envs' fused
-#   launches (packed and columns); shards = RockSample(7,8) at 2^17 / 2^18 / 2^19 lanes.
+#   launches (packed and columns); shards = RockSample(7,8) at 2^17 / 2^18 / 2^19 lanes; packed = the headline kernel alone
+#   (RockSample(7,8), packed records, both launch shapes) with its HBM byte passes: what a change to the lane step re-records.
 #   Workloads that are not re-recorded are carried over from the newest profiles/*_pmc_valu.json, each with the source hash
 #   it was recorded under (bench.py: counters_stale).
 TAG=${1:-pmcv}
@@ -19,11 +20,18 @@ rm -rf $W; mkdir -p $OUT $W
 cd /tmp
 SQ1="SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY"
 SQ2="SQ_BUSY_CYCLES SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_SCA SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD SQ_INSTS_SMEM SQ_WAIT_INST_LDS GRBM_GUI_ACTIVE"
+pass() {   # log, command...: one profiled run under its own time limit; a run that was killed, aborted or hit its limit ends
+           # the script — nothing more is started on a card that may have faulted
+  local log=$1; shift
+  timeout -k 10 600 "$@" > $log 2>&1
+  local rc=$?
+  case $rc in 124|134|137|139) echo "pass ended with status $rc ($log): stopping"; tail -5 $log; exit $rc ;; esac
+}
 run() {   # name, bench args...
   local name=$1; shift
   mkdir -p $W/$name
-  timeout 600 rocprofv3 --kernel-trace --pmc $SQ1 -d $W/$name/p1 -o p1 -- python $REPO/bench.py "$@" > $W/$name/p1.log 2>&1
-  timeout 600 rocprofv3 --kernel-trace --pmc $SQ2 -d $W/$name/p2 -o p2 -- python $REPO/bench.py "$@" > $W/$name/p2.log 2>&1
+  pass $W/$name/p1.log rocprofv3 --kernel-trace --pmc $SQ1 -d $W/$name/p1 -o p1 -- python $REPO/bench.py "$@"
+  pass $W/$name/p2.log rocprofv3 --kernel-trace --pmc $SQ2 -d $W/$name/p2 -o p2 -- python $REPO/bench.py "$@"
   echo "$name: $*" >> $W/commands.txt
 }
 SQ3="TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_STALL_sum TCC_EA0_WRREQ_64B_sum TCC_EA0_WR_UNCACHED_32B_sum"
@@ -33,14 +41,14 @@ stalls() {   # name, bench args...: what the store path waits for (L2 write requ
              # know costs one pass, not all
   local name=$1; shift
   mkdir -p $W/$name
-  timeout 600 rocprofv3 --kernel-trace --pmc $SQ3 -d $W/$name/p3 -o p3 -- python $REPO/bench.py "$@" > $W/$name/p3.log 2>&1
-  timeout 600 rocprofv3 --kernel-trace --pmc $SQ4 -d $W/$name/p4 -o p4 -- python $REPO/bench.py "$@" > $W/$name/p4.log 2>&1
+  pass $W/$name/p3.log rocprofv3 --kernel-trace --pmc $SQ3 -d $W/$name/p3 -o p3 -- python $REPO/bench.py "$@"
+  pass $W/$name/p4.log rocprofv3 --kernel-trace --pmc $SQ4 -d $W/$name/p4 -o p4 -- python $REPO/bench.py "$@"
 }
 traffic() {   # name, bench args...: FETCH_SIZE and WRITE_SIZE in separate passes
   local name=$1; shift
   mkdir -p $W/$name/pmc_fetch $W/$name/pmc_write
-  timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $W/$name/pmc_fetch -o f -- python $REPO/bench.py "$@" > $W/$name/f.log 2>&1
-  timeout 600 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $W/$name/pmc_write -o w -- python $REPO/bench.py "$@" > $W/$name/w.log 2>&1
+  pass $W/$name/f.log rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $W/$name/pmc_fetch -o f -- python $REPO/bench.py "$@"
+  pass $W/$name/w.log rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $W/$name/pmc_write -o w -- python $REPO/bench.py "$@"
 }
 sfx() { if [ "$1" = columns ]; then echo ""; else echo "_$1"; fi; }
 S256="--prewarm 0 --warmup 256 --steps 1024 --seeds 0 --repeats 1 --no-cpu-baseline --no-extras"
@@ -68,6 +76,11 @@ for set in $SETS; do
     traffic step64_rock --env rock --layout columns $S256
     stalls step256_rock_packed --env rock --layout packed $S256; stalls step256_rock_narrow --env rock --layout narrow $S256
     stalls step64_rock --env rock --layout columns $S256; stalls step64_rock_blocked --env rock --layout blocked $S256 ;;
+  packed)   # the headline kernel alone, both launch shapes, with the byte counters `traffic` quotes
+    run step256_rock_packed --env rock --layout packed $S256
+    run step20_rock_packed --env rock --layout packed $S20
+    traffic step20_rock_packed --env rock --layout packed $S20
+    traffic step256_rock_packed --env rock --layout packed $S256 ;;
   sinks)    # the headline workload's sinks at 256 steps per launch only (a quick A/B of what a sink costs)
     for l in packed narrow returns; do run step256_rock$(sfx $l) --env rock --layout $l $S256; done ;;
   envs)

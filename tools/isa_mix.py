@@ -38,7 +38,7 @@ ALIAS = {
     "v_lshl_or_b32": "v_lshl_or_b32", "v_and_or_b32": "v_and_or_b32", "v_or3_b32": "v_or3_b32", "v_add3_u32": "v_add3_u32",
     "v_lshl_add_u32": "v_lshl_add_u32", "v_add_lshl_u32": "v_lshl_add_u32", "v_xad_u32": "v_xad_u32",
     "v_mul_hi_u32": "v_mul_hi_u32", "v_mul_lo_u32": "v_mul_lo_u32", "v_mad_u64_u32": "v_mad_u64_u32", "v_mul_u32_u24": "v_mad_u32_u24",
-    "v_mad_u32_u24": "v_mad_u32_u24", "v_mul_hi_u32_u24": "v_mad_u32_u24",
+    "v_mad_u32_u24": "v_mad_u32_u24", "v_mul_hi_u32_u24": "v_mad_u32_u24", "v_mad_i32_i24": "v_mad_u32_u24", "v_mul_i32_i24": "v_mad_u32_u24",
     "v_sad_u8": "v_sad_u8", "v_bfe_u32": "v_bfe_u32", "v_bfe_i32": "v_bfe_u32", "v_mov_b32": "v_mov_b32", "v_bcnt_u32_b32": "v_bcnt_u32_b32",
     "v_alignbit_b32": "v_alignbit_b32", "v_min_u32": "v_min_u32", "v_max_u32": "v_min_u32", "v_min_i32": "v_min_u32", "v_max_i32": "v_min_u32",
     "v_min3_u32": "v_add3_u32", "v_perm_b32": "v_perm_b32", "v_lshlrev_b64": "v_lshlrev_b64", "v_lshrrev_b64": "v_lshlrev_b64",
@@ -122,7 +122,9 @@ def blocks_of(lines):
     return blocks
 
 
-PHILOX_OPS = ("v_mad_u64_u32", "v_bitop3_b32")
+# a Philox round is two 32 x 32 -> 64 multiplies and the xors around them; the compiler writes a multiply by a constant held
+# in a scalar register as v_mad_u64_u32, and one whose other factor came through a register move as v_mul_lo / v_mul_hi
+PHILOX_OPS = ("v_mad_u64_u32", "v_mul_lo_u32", "v_mul_hi_u32", "v_bitop3_b32", "v_xor_b32")
 
 
 def is_tie_path(prev, b):
@@ -132,7 +134,7 @@ def is_tie_path(prev, b):
     if prev is None or not prev["insts"] or prev["insts"][-1] != "s_cbranch_execz":
         return False
     v = [i for i in b["insts"] if i.startswith("v_")]
-    return len(v) >= 30 and sum(base(i) in PHILOX_OPS for i in v) >= 0.7 * len(v)
+    return len(v) >= 30 and sum(base(i) in PHILOX_OPS for i in v) >= 0.65 * len(v)
 
 
 def hot_loop(blocks):
