@@ -154,27 +154,32 @@ struct RockEnv {
         uint32_t codes = w & 0xAAAAAAAAu;
         // A tied rotation is 1, twenty-six zeros, five free bits: at most six bits set in the word (2.7e-4 per word);
         // only then look closer
-        if (__popc(w) <= 6) {
-            bool have_lo = false;
-            uint32_t l = 0;
-            for (int j = 0; j < K; ++j) {
-                const uint32_t rot = (uint32_t)(2 * j + 2) & 31u;
-                if (rock_code_hi(__builtin_rotateright32(w, rot)) != 3u) continue;
-                if (!have_lo) {
-                    // The low-word block of an auto-reset IS the block a sensor tie of the same step reads: left as one
-                    // expression, the compiler merges the two 2^-27 paths' Philox calls and computes the block
-                    // unconditionally, every step (one lane per thread, 2^18 lanes: 0.79 -> 0.97 us per step).  The lane id
-                    // passes through an opaque register move, so this call stays where it is needed.
-                    uint32_t lane_ = lane;
-                    asm volatile("" : "+v"(lane_));
-                    l = elem(reset_block<AUTO>(rare_key(key), lane_, 1u), lane & 3u);
-                    have_lo = true;
-                }
-                const uint32_t c = rock_code_lo(__builtin_rotateright32(l, rot));
-                codes = (codes & ~(3u << (2 * j))) | (c << (2 * j));
-            }
-        }
+        if (__popc(w) <= 6) reset_ties<AUTO>(w, key, lane, K, codes, 0);
         return codes & (K >= 16 ? 0xFFFFFFFFu : ((1u << (2 * K)) - 1u));      // rocks that exist (wave-uniform)
+    }
+    // ... the closer look: the codes of the rocks whose rotation of `w` ties, decided by the low word and put into `word`,
+    // which holds rock j's code at bit `base` + 2 j
+    template <bool AUTO>
+    static __device__ __forceinline__ void reset_ties(uint32_t w, const RngKey &key, uint32_t lane, int K, uint32_t &word, int base)
+    {
+        bool have_lo = false;
+        uint32_t l = 0;
+        for (int j = 0; j < K; ++j) {
+            const uint32_t rot = (uint32_t)(2 * j + 2) & 31u;
+            if (rock_code_hi(__builtin_rotateright32(w, rot)) != 3u) continue;
+            if (!have_lo) {
+                // The low-word block of an auto-reset IS the block a sensor tie of the same step reads: left as one
+                // expression, the compiler merges the two 2^-27 paths' Philox calls and computes the block
+                // unconditionally, every step (one lane per thread, 2^18 lanes: 0.79 -> 0.97 us per step).  The lane id
+                // passes through an opaque register move, so this call stays where it is needed.
+                uint32_t lane_ = lane;
+                asm volatile("" : "+v"(lane_));
+                l = elem(reset_block<AUTO>(rare_key(key), lane_, 1u), lane & 3u);
+                have_lo = true;
+            }
+            const uint32_t c = rock_code_lo(__builtin_rotateright32(l, rot));
+            word = (word & ~(3u << (base + 2 * j))) | (c << (base + 2 * j));
+        }
     }
     // block `j2` (0 = sensor / gate high words, 1 = their low words, 2 / 3 = StochasticRock's sensor) of lane's quad
     static __device__ __forceinline__ uint4 quad_block(const RngKey &key, uint32_t lane, uint32_t j2)
@@ -193,6 +198,25 @@ struct RockEnv {
         if (min(min(__popc(R[0]), __popc(R[1])), min(__popc(R[2]), __popc(R[3]))) <= 6) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) codes[e] = reset_codes<true>(R[e], key, first + (uint32_t)e, K);
+        }
+    }
+    // The fresh episodes a step may hand the N lanes of one thread (N = 4: the quad first .. first + 3, N = 2: half of it), as
+    // state words (one state word; ROT: in the rotated layout of build_rec_tab<true>) from the lanes' words R of the step's
+    // sensor block; `start`: the start cell's position byte where the layout has it.  ONE branch for the ties; off it a lane
+    // costs one v_and_or_b32 (ROT, `start` in a vector register) — the codes stay where the word has them.
+    template <int N, bool ROT>
+    static __device__ __forceinline__ void fresh_states(const uint32_t (&R)[N], const RngKey &key, uint32_t first, int K,
+                                                        uint32_t start, uint32_t (&fresh)[N])
+    {
+        const uint32_t exist = K >= 16 ? 0xFFFFFFFFu : ((1u << (2 * K)) - 1u);
+        auto word = [&](uint32_t codes) { return ROT ? (codes | start) : (start | (codes << 8)); };
+        int fewest = __popc(R[0]);
+#pragma unroll
+        for (int e = 0; e < N; ++e) { fresh[e] = word(R[e] & (0xAAAAAAAAu & exist)); fewest = min(fewest, (int)__popc(R[e])); }
+        if (fewest <= 6) {
+#pragma unroll
+            for (int e = 0; e < N; ++e)
+                if (__popc(R[e]) <= 6) reset_ties<true>(R[e], key, first + (uint32_t)e, K, fresh[e], ROT ? 0 : 8);
         }
     }
     // rock.py:236-241 reset -> 266-271 _get_init_state -> 78-86 Rock.__init__:
@@ -482,6 +506,13 @@ struct RockEnv {
     //                SAMPLE with a rock underfoot and q != 1 collects it, code -> 1, which is the step c = 1 - q at the same
     //                offset, and its record is 0x00F60004 - q * 0x00760000 (reward byte 0xF6 = -10 or 0x0A = +10, action 4).
     // done is read off the finished record (>= 1 << 24).
+    // The quad-per-thread loops (steps_quad_kernel) take the step in its two halves — rec_lookup for all of a thread's lanes, one
+    // wait, the compares, ONE branch for the lanes whose draw ties, rec_finish — and keep the state word rotated right by 8 in
+    // registers (ROT: rock j's code at bit 2 j, the position byte on top; one v_alignbit_b32 per lane after the launch's load
+    // and one before its store): the entry's address is one v_alignbit_b32 and one v_and_b32 (a << 11 | position << 3), and a
+    // fresh episode one v_and_or_b32 of the lane's sensor word — its rocks' codes are where the word has them — instead of a
+    // v_and_b32 and a v_lshl_or_b32: 19 + 1 vector instructions per lane-step there.  The table differs in its bit offsets only
+    // (build_rec_tab<true>).
     // Two state words keep 4-byte entries (21 x 256 x 8 = 42 KB would leave three workgroups per CU), test the action, and
     // look the reward byte up by outcome code with one v_perm_b32 in an 8-byte constant; that branch is as it was.
     static constexpr uint32_t REC_LUT_LO = 0x0A0A9CF6u, REC_LUT_HI = 0x00000000u;   // reward byte by outcome code 0..7 (two state words)
@@ -493,8 +524,17 @@ struct RockEnv {
         const uint32_t rbyte = (((uint64_t)REC_LUT_HI << 32 | REC_LUT_LO) >> (8u * oc)) & 0xFFu;
         return off | (((uint32_t)c & 3u) << 5) | (ob_mask << 8) | (rbyte << 16) | ((oc & 1u) << 24);
     }
+    // ROT: the table of a loop that keeps the state word rotated right by 8 in registers (steps_quad_kernel, one state word):
+    // rock j's code at bit 2 j, the position byte on top at bits 24-31 (ROT_POS).  The entries are the same but for their bit
+    // offsets: a move's 24 (x) or 28 (y), a rock's 2 j.  No step carries out of its field in either layout: a move that stays
+    // inside keeps its nibble (and y is the word's top nibble), and a SAMPLE takes a code of 0 or 2 to 1 — + 1 on 0, - 1 on 2,
+    // neither leaves the two bits — so the last rock of a 12-rock board, at bits 22-23 right under x, never reaches the position.
+    static constexpr uint32_t ROT_POS = 24u;
+    template <bool ROT = false>
     static __device__ __forceinline__ void build_rec_tab(RecTab &tab, const Shared &sh, const Params &p, int pos)
     {
+        static_assert(!ROT || W == 1, "the rotated layout is the one-state-word loops'");
+        constexpr uint32_t POS0 = ROT ? ROT_POS : 0u, ROCK0 = ROT ? 0u : 8u;     // bit offsets of x and of rock 0's code
         const uint32_t x = (uint32_t)pos & 15u, y = (uint32_t)pos >> 4, size = (uint32_t)p.size, K = (uint32_t)p.num_rocks;
         const int id = sh.grid[x * 16 + y];
         const uint32_t NOTHING = 6u << 28, PENALTY = (STOCH ? 6u : 1u) << 28, EXIT_EAST = 3u << 28;
@@ -507,14 +547,14 @@ struct RockEnv {
                 e = inside ? (((uint32_t)pos ^ (nx | (ny << 4))) | NOTHING) : (a == 1 ? EXIT_EAST : PENALTY);
                 e |= NO_TIE;
                 // x +- 1 is the state word +- 1, y +- 1 is +- 1 << 4 (no carry leaves the nibble of a move that stays inside)
-                f = rec_f((a & 1) ? 0u : 4u, inside ? (a < 2 ? 1 : -1) : 0, 0u, e >> 28 & 7u);
+                f = rec_f(POS0 + ((a & 1) ? 0u : 4u), inside ? (a < 2 ? 1 : -1) : 0, 0u, e >> 28 & 7u);
             } else if (a == 4) {
                 const bool rock = (uint32_t)id < K;
                 e = (rock ? ((8u + 2u * (uint32_t)id) | 0x80000000u) : 0u) | PENALTY | NO_TIE;
-                f = rec_f(rock ? 8u + 2u * (uint32_t)id : 0u, 0, 0u, e >> 28 & 7u);
+                f = rec_f(rock ? ROCK0 + 2u * (uint32_t)id : 0u, 0, 0u, e >> 28 & 7u);
             } else {
                 e = sh.thr[__builtin_amdgcn_sad_u8(x | (y << 8), sh.rpos[a - 5], 0u) & 31u].x | NOTHING;
-                f = rec_f(2u * (uint32_t)a - 2u, 0, 3u, 6u);
+                f = rec_f(ROCK0 + 2u * (uint32_t)(a - 5), 0, 3u, 6u);
             }
             if constexpr (W == 1) tab.e[a][pos] = make_uint2(e, f);
             else tab.e[a][pos] = e;
@@ -524,32 +564,61 @@ struct RockEnv {
     // H: the lane's sensor high word; `lo` yields its low word (a tie, 2^-27 per CHECK).  Two state words (K > 12): the rock
     // codes run on into the upper word (rock j at bits 8 + 2 j), a code never straddles the words, and the word a SAMPLE or
     // a CHECK reads is a select on bit 5 of its bit offset.
+    // The one-state-word lane step in its two halves, for the loops that issue the table reads of all of a thread's lanes before
+    // they use the first (steps_quad_kernel): rec_lookup reads the entry, rec_kh is what the entry's first word compares with
+    // (`correct` = rec_kh(H) < e, a tie = rec_kh(H) == e: then the low word decides, against rec_thr_lo), rec_finish makes the
+    // record and the new state.  ROT: the state word is kept rotated (build_rec_tab<true>).
+    template <bool ROT = false>
+    static __device__ __forceinline__ uint2 rec_lookup(const RecTab &tab, uint32_t s, uint32_t a)
+    {
+        if constexpr (ROT) {
+            // the entry's byte offset a << 11 | position << 3 in one v_alignbit_b32 (the position byte is the word's top) and one
+            // v_and_b32 that clears the three code bits that came along
+            const uint32_t off = __builtin_amdgcn_alignbit(a, s, ROT_POS - 3u) & ~7u;
+            return *reinterpret_cast<const uint2 *>(reinterpret_cast<const char *>(&tab.e[0][0]) + off);
+        } else return tab.e[a][s & 0xFFu];
+    }
+    static __device__ __forceinline__ uint32_t rec_kh(uint32_t H) { return __builtin_amdgcn_alignbit(12u, H, 5u); }   // (H >> 5) | 6 << 28
+    // (ROT: the measured rock is read off the entry — its offset is 2 (a - 5) — so that a tape-driven loop's rare path does not
+    // keep the action, i.e. a tape row it wants to load over, alive)
+    template <bool ROT = false>
+    static __device__ __forceinline__ uint32_t rec_thr_lo(const Shared &sh, uint32_t s, uint32_t a, uint32_t f)
+    {
+        if constexpr (ROT) return thr_lo_of(sh, State{(S)(s >> ROT_POS)}, (int)((f & 31u) >> 1));
+        else return thr_lo_of(sh, State{(S)s}, (int)a - 5);
+    }
+    static __device__ __forceinline__ void rec_finish(const uint2 ef, uint32_t &s, uint32_t a, bool correct, uint32_t fresh, uint32_t &rec)
+    {
+        const uint32_t e = ef.x, f = ef.y;
+        // the code of the rock this step is about — under a SAMPLE, or the one a CHECK measures — read at the entry's offset
+        // (a move's entry points at the position nibble it changes: whatever this reads there is not used)
+        const uint32_t q = __builtin_amdgcn_ubfe(s, f, 2u);
+        const bool ok = ((int32_t)e < 0) & (q != 1u);                       // SAMPLE: an uncollected rock with an id < K is underfoot
+        // the record when no live rock is sampled: the entry's own bytes, of its two ob bits the one the reading gives
+        // (CHECK rock a - 5, rock.py:171-175, 401-407: good = its code is 2)
+        const uint32_t keep = ((q == 2u) == correct) ? 0xFFFFFE00u : 0xFFFFFD00u;
+        const uint32_t rfb = (f & keep) | a;
+        // a sampled rock's code IS its outcome: 0 -> -10 (0xF6), 2 -> +10 (0x0A), never done; the action byte is SAMPLE's
+        const uint32_t rok = 0x00F60004u - q * 0x00760000u;
+        rec = ok ? rok : rfb;
+        // the state moves by a step of -1, 0 or +1 at the entry's offset: a move's nibble, or a sampled rock's code -> 1
+        const int c = ok ? 1 - (int)q : __builtin_amdgcn_sbfe((int)f, 5u, 2u);
+        const uint32_t moved = s + ((uint32_t)c << (f & 31u));
+        s = rec >= (1u << 24) ? fresh : moved;                              // done: byte 3 of the finished record
+    }
     template <class LowWord>
     static __device__ __forceinline__ void step_rec(const Shared &sh, const RecTab &tab, S &s, uint32_t a, uint32_t H, S fresh,
                                                     uint32_t &rec, LowWord lo)
     {
         const uint32_t s_lo = (uint32_t)s, s_hi = W == 2 ? (uint32_t)((uint64_t)s >> 32) : 0u;
         if constexpr (W == 1) {
-            const uint2 ef = tab.e[a][s_lo & 0xFFu];
-            const uint32_t e = ef.x, f = ef.y;
-            // the code of the rock this step is about — under a SAMPLE, or the one a CHECK measures — read at the entry's offset
-            // (a move's entry points at the position nibble it changes: whatever this reads there is not used)
-            const uint32_t q = __builtin_amdgcn_ubfe(s_lo, f, 2u);
-            const bool ok = ((int32_t)e < 0) & (q != 1u);                       // SAMPLE: an uncollected rock with an id < K is underfoot
-            // CHECK rock a - 5 (rock.py:171-175, 401-407): good = its code is 2
-            const uint32_t kh = __builtin_amdgcn_alignbit(12u, H, 5u);          // (H >> 5) | 6 << 28: compares with the entry itself
-            bool correct = kh < e;
-            if (kh == e) correct = (lo() >> 6) <= thr_lo_of(sh, State{s}, (int)a - 5);   // a CHECK only (NO_TIE); probability 2^-27
-            // the record when no live rock is sampled: the entry's own bytes, of its two ob bits the one the reading gives
-            const uint32_t keep = ((q == 2u) == correct) ? 0xFFFFFE00u : 0xFFFFFD00u;
-            const uint32_t rfb = (f & keep) | a;
-            // a sampled rock's code IS its outcome: 0 -> -10 (0xF6), 2 -> +10 (0x0A), never done; the action byte is SAMPLE's
-            const uint32_t rok = 0x00F60004u - q * 0x00760000u;
-            rec = ok ? rok : rfb;
-            // the state moves by a step of -1, 0 or +1 at the entry's offset: a move's nibble, or a sampled rock's code -> 1
-            const int c = ok ? 1 - (int)q : __builtin_amdgcn_sbfe((int)f, 5u, 2u);
-            const uint32_t moved = s_lo + ((uint32_t)c << (f & 31u));
-            s = rec >= (1u << 24) ? fresh : (S)moved;                           // done: byte 3 of the finished record
+            const uint2 ef = rec_lookup(tab, s_lo, a);
+            const uint32_t kh = rec_kh(H);                                      // compares with the entry itself
+            bool correct = kh < ef.x;
+            if (kh == ef.x) correct = (lo() >> 6) <= rec_thr_lo(sh, s_lo, a, ef.y);   // a CHECK only (NO_TIE); probability 2^-27
+            uint32_t sn = s_lo;
+            rec_finish(ef, sn, a, correct, (uint32_t)fresh, rec);
+            s = (S)sn;
         } else {
             const uint32_t e = tab.e[a][s_lo & 0xFFu];
             // SAMPLE (rock.py:160-169): the cell's rock code, read at the entry's offset (entries of the other classes: the

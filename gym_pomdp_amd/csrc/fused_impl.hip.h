@@ -10,11 +10,11 @@ namespace pomdp {
 // The thread's place in the batch, its sink and its policy; the prologue around the first actions; the per-step key; the
 // epilogue of a step (the policy's next actions become the current ones) and of the launch.  LPT lanes per thread: 4, or 2
 // for BattleShip's small shards.  A contract change touches this and the env's own lane step, not six loops.
-template <class L, class Pol, int LPT = 4>
+template <class L, class Pol, int LPT = 4, bool SROW = false>   // SROW: packed records leave through a scalar row base (traj_out.hip.h)
 struct FusedCtx {
     uint32_t l0, glane0;                                     // the thread's first lane within the shard / its global id
     uint64_t t0;                                             // call counter of the launch's first step
-    typename lanes_out<L, LPT>::type out;
+    typename lanes_out<L, LPT, SROW>::type out;
     typename lanes_policy<Pol, LPT>::type pol;
     uint32_t n_bad;                                          // tape only: out-of-range actions met
     __device__ __forceinline__ FusedCtx(int32_t *action, int32_t *ob, void *reward, uint8_t *done, int64_t rec, uint32_t lane0,
@@ -358,6 +358,10 @@ __global__ __launch_bounds__(BLOCK) void steps_kernel(uint32_t *__restrict__ sta
 // actions come in the same way.  The lane step is the table-driven one.  Full workgroups of 1024 lanes and auto-reset
 // only (the launcher's SIMPLE conditions).  Same results as steps_kernel: the mapping of lanes to threads is invisible
 // to a lane's random words.
+// One state word (round 13): the lane step runs in two phases — the table reads of all of the thread's lanes, ONE wait, every
+// compare, ONE exec-masked branch for the lanes whose sensor draw the high word leaves undecided (with the reset-tie filter:
+// two per step, where each lane had its own read -> wait -> compare -> branch), then the records — on a state word kept
+// rotated in registers (rock.hip.h: RecTab), and packed records leave through a scalar row base (traj_out.hip.h: PackedRowOut).
 // LPT = 2 (round 6): HALF a quad per thread, for the shards that leave the quad loop two waves per SIMD or fewer (2^19 lanes
 // — half of a 2^20-lane batch — ran the pooled two-lanes-per-thread steps_kernel at 0.46 of its issue floor).  The quad's
 // STEP block (and StochasticRock's gate block) is time-shared by the quad's two threads exactly like the policy's block
@@ -373,16 +377,19 @@ __global__ __launch_bounds__(BLOCK) void steps_quad_kernel(uint32_t *__restrict_
 {
     static_assert(LPT == 4 || LPT == 2, "a quad or half a quad per thread");
     constexpr int W = Env::WORDS;
+    // one state word: the loop keeps it rotated right by 8 — rock codes from bit 0, the position byte on top — so that a fresh
+    // episode is one v_and_or_b32 of the lane's sensor word (RockEnv::build_rec_tab<true>); memory keeps its layout
+    constexpr bool ROT = W == 1;
     using S = typename Env::S;
     __shared__ typename Env::Shared sh;
-    // the lane step yields the lane's packed record straight from RecTab (RockEnv::step_rec, 20 vector instructions per
-    // lane-step with one state word)
+    // the lane step yields the lane's packed record straight from RecTab (one state word: RockEnv::rec_lookup / rec_finish, 19
+    // vector instructions per lane-step and one for the fresh episode it may need; two: RockEnv::step_rec)
     __shared__ typename Env::RecTab tab;
     const uint32_t n_act = (uint32_t)Env::n_actions(p);
     // a quad per thread on a tape: the loop unrolled by two, the tape read two steps ahead (TapeQuadAhead)
     constexpr bool AHEAD2 = Pol::TAPE && LPT == 4;
     using PolT = typename std::conditional<AHEAD2, TapeQuadAhead, Pol>::type;
-    FusedCtx<L, PolT, LPT> cx(action, ob, reward, done, rec, lane0, key0, akey0, n_act, k_steps, tape);
+    FusedCtx<L, PolT, LPT, true> cx(action, ob, reward, done, rec, lane0, key0, akey0, n_act, k_steps, tape);
     const uint32_t l0 = cx.l0, glane0 = cx.glane0;           // the thread's first lane within the shard; its global id (a multiple of LPT)
     const uint32_t e0 = LPT == 4 ? 0u : (glane0 & 2u);       // ... and that lane's element of its quad's blocks (LPT = 2: 0 or 2)
     typename Env::State st[LPT];
@@ -405,14 +412,21 @@ __global__ __launch_bounds__(BLOCK) void steps_quad_kernel(uint32_t *__restrict_
         }
         cx.first(gen_first, a_cur);
 #pragma unroll
-        for (int j = 0; j < LPT; ++j) st[j].s = (S)((uint64_t)s_lo[j] | ((uint64_t)s_hi[j] << 32));
+        for (int j = 0; j < LPT; ++j) {
+            if constexpr (ROT) st[j].s = __builtin_amdgcn_alignbit(s_lo[j], s_lo[j], 8u);
+            else st[j].s = (S)((uint64_t)s_lo[j] | ((uint64_t)s_hi[j] << 32));
+        }
     }
     Env::stage(sh, p, (int)threadIdx.x);
     __syncthreads();
-    Env::build_rec_tab(tab, sh, p, (int)threadIdx.x);
+    Env::template build_rec_tab<ROT>(tab, sh, p, (int)threadIdx.x);
     __syncthreads();
     const int K = p.num_rocks;
     const uint32_t start = (uint32_t)p.start_x | ((uint32_t)p.start_y << 4);
+    // ... where the rotated layout has it, in a vector register: (H & codes) | start is then one v_and_or_b32 (two scalar
+    // operands do not fit one instruction)
+    uint32_t start_rot = start << (ROT ? Env::ROT_POS : 0u);
+    if constexpr (ROT) asm volatile("" : "+v"(start_rot));
     const LoopPrio prio(k_steps);
     constexpr uint32_t SENSOR_BLOCK = Env::SENSOR_BLOCK;
     // a quad per thread: the quad's STEP blocks have counter words 0 and 3 fixed for the launch (philox4x32_10_fixed)
@@ -449,32 +463,80 @@ __global__ __launch_bounds__(BLOCK) void steps_quad_kernel(uint32_t *__restrict_
                 acts[j] = Env::k53_le(G[j], (uint32_t)(p.act_thr >> 26), (uint32_t)p.act_thr & Env::LO_MASK,
                                       [&]() { return Env::elem(Env::quad_block(key, glane0, 1u), e0 + (uint32_t)j); }) != (p.act_gt != 0);
         }
-        uint32_t codes[LPT], rec[LPT], a_taken[LPT];
+        uint32_t rec[LPT], a_taken[LPT];
 #pragma unroll
         for (int j = 0; j < LPT; ++j) a_taken[j] = (uint32_t)a_cur[j];
-        if constexpr (LPT == 4) Env::reset_codes4(H, key, glane0, K, codes);
-        else {
+        // a tape may hold anything: an out-of-range action leaves the lane untouched, (ob, reward, done) = (0, 0, 0), and is counted
+        bool valid[LPT];
 #pragma unroll
-            for (int j = 0; j < LPT; ++j) codes[j] = Env::template reset_codes<true>(H[j], key, glane0 + (uint32_t)j, K);
-        }
+        for (int j = 0; j < LPT; ++j) valid[j] = !Pol::TAPE || a_taken[j] < n_act;
+        auto low_word = [&](int j) __attribute__((always_inline)) {
+            return Env::elem(Env::quad_block(rare_key(key), glane0 + (uint32_t)j, SENSOR_BLOCK + 1u), e0 + (uint32_t)j);
+        };
+        if constexpr (ROT) {
+            // the lane step in two phases: every table read of the thread first — one wait for all of them — then every
+            // compare, ONE branch for the lanes whose sensor draw the high word leaves undecided (2^-27 per CHECK), then the records
+            uint32_t fresh[LPT], kh[LPT], sn[LPT];
+            uint2 ef[LPT];
+            bool correct[LPT], tie[LPT], any_tie = false;
+            Env::template fresh_states<LPT, true>(H, key, glane0, K, start_rot, fresh);
 #pragma unroll
-        for (int j = 0; j < LPT; ++j) {
-            const uint32_t lane = glane0 + (uint32_t)j;
-            S sj = st[j].s;
-            // a tape may hold anything: an out-of-range action leaves the lane untouched, (ob, reward, done) = (0, 0, 0), and is counted
-            const bool valid = !Pol::TAPE || a_taken[j] < n_act;
-            Env::step_rec(sh, tab, sj, valid ? a_taken[j] : 0u, H[j], (S)((uint64_t)start | ((uint64_t)codes[j] << 8)), rec[j],
-                          [&]() { return Env::elem(Env::quad_block(rare_key(key), lane, SENSOR_BLOCK + 1u), e0 + (uint32_t)j); });
-            if constexpr (Env::STOCHASTIC) {                                // the gate said no (rock.py:443): nothing happens
-                sj = acts[j] ? sj : st[j].s;
-                rec[j] = acts[j] ? rec[j] : a_taken[j];
+            for (int j = 0; j < LPT; ++j) ef[j] = Env::template rec_lookup<true>(tab, st[j].s, valid[j] ? a_taken[j] : 0u);
+            if constexpr (LPT == 4) asm volatile("" : "+v"(ef[0].x), "+v"(ef[0].y), "+v"(ef[1].x), "+v"(ef[1].y), "+v"(ef[2].x), "+v"(ef[2].y), "+v"(ef[3].x), "+v"(ef[3].y));
+            else asm volatile("" : "+v"(ef[0].x), "+v"(ef[0].y), "+v"(ef[1].x), "+v"(ef[1].y));   // all of them have landed: one wait
+#pragma unroll
+            for (int j = 0; j < LPT; ++j) {
+                kh[j] = Env::rec_kh(H[j]);
+                correct[j] = kh[j] < ef[j].x;
+                tie[j] = kh[j] == ef[j].x;                                   // a CHECK only (NO_TIE)
+                any_tie |= tie[j];
             }
-            if constexpr (Pol::TAPE) {
-                sj = valid ? sj : st[j].s;
-                rec[j] = valid ? rec[j] : a_taken[j];
-                cx.n_bad += (uint32_t)!valid;
+            if (any_tie) {
+#pragma unroll
+                for (int j = 0; j < LPT; ++j)
+                    if (tie[j]) correct[j] = (low_word(j) >> 6) <= Env::template rec_thr_lo<true>(sh, st[j].s, a_taken[j], ef[j].y);
             }
-            st[j].s = sj;
+#pragma unroll
+            for (int j = 0; j < LPT; ++j) {
+                sn[j] = st[j].s;
+                Env::rec_finish(ef[j], sn[j], valid[j] ? a_taken[j] : 0u, correct[j], fresh[j], rec[j]);
+            }
+#pragma unroll
+            for (int j = 0; j < LPT; ++j) {
+                if constexpr (Env::STOCHASTIC) {                            // the gate said no (rock.py:443): nothing happens
+                    sn[j] = acts[j] ? sn[j] : st[j].s;
+                    rec[j] = acts[j] ? rec[j] : a_taken[j];
+                }
+                if constexpr (Pol::TAPE) {
+                    sn[j] = valid[j] ? sn[j] : st[j].s;
+                    rec[j] = valid[j] ? rec[j] : a_taken[j];
+                    cx.n_bad += (uint32_t)!valid[j];
+                }
+                st[j].s = sn[j];
+            }
+        } else {
+            uint32_t codes[LPT];
+            if constexpr (LPT == 4) Env::reset_codes4(H, key, glane0, K, codes);
+            else {
+#pragma unroll
+                for (int j = 0; j < LPT; ++j) codes[j] = Env::template reset_codes<true>(H[j], key, glane0 + (uint32_t)j, K);
+            }
+#pragma unroll
+            for (int j = 0; j < LPT; ++j) {
+                S sj = st[j].s;
+                Env::step_rec(sh, tab, sj, valid[j] ? a_taken[j] : 0u, H[j], (S)((uint64_t)start | ((uint64_t)codes[j] << 8)), rec[j],
+                              [&]() { return low_word(j); });
+                if constexpr (Env::STOCHASTIC) {                                // the gate said no (rock.py:443): nothing happens
+                    sj = acts[j] ? sj : st[j].s;
+                    rec[j] = acts[j] ? rec[j] : a_taken[j];
+                }
+                if constexpr (Pol::TAPE) {
+                    sj = valid[j] ? sj : st[j].s;
+                    rec[j] = valid[j] ? rec[j] : a_taken[j];
+                    cx.n_bad += (uint32_t)!valid[j];
+                }
+                st[j].s = sj;
+            }
         }
         cx.out.put_records(rec, a_next);
         if constexpr (AHEAD2) {
@@ -493,15 +555,18 @@ __global__ __launch_bounds__(BLOCK) void steps_quad_kernel(uint32_t *__restrict_
     } else {
         POMDP_FUSED_STEP_LOOP(prio, s) step_body(s, std::integral_constant<int, 0>{});
     }
-    // the state is the loop's carry: it reaches memory once
+    // the state is the loop's carry: it reaches memory once (one state word: rotated back into its memory layout)
     cx.finish(k_steps);
+    uint32_t w_lo[LPT];
+#pragma unroll
+    for (int j = 0; j < LPT; ++j) w_lo[j] = ROT ? __builtin_amdgcn_alignbit((uint32_t)st[j].s, (uint32_t)st[j].s, 24u) : (uint32_t)st[j].s;
     if constexpr (LPT == 4) {
-        st_stream4(state + l0, (uint32_t)st[0].s, (uint32_t)st[1].s, (uint32_t)st[2].s, (uint32_t)st[3].s);
+        st_stream4(state + l0, w_lo[0], w_lo[1], w_lo[2], w_lo[3]);
         if (W == 2)
             st_stream4(state + n + l0, (uint32_t)((uint64_t)st[0].s >> 32), (uint32_t)((uint64_t)st[1].s >> 32),
                        (uint32_t)((uint64_t)st[2].s >> 32), (uint32_t)((uint64_t)st[3].s >> 32));
     } else {
-        st_stream2(state + l0, (uint32_t)st[0].s, (uint32_t)st[1].s);
+        st_stream2(state + l0, w_lo[0], w_lo[1]);
         if (W == 2) st_stream2(state + n + l0, (uint32_t)((uint64_t)st[0].s >> 32), (uint32_t)((uint64_t)st[1].s >> 32));
     }
 }

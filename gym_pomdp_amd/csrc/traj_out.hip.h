@@ -590,12 +590,46 @@ template <class Env> struct PairOut<Returns<Env>> {
             (void)__hip_atomic_fetch_add(cnt_w + pitch + j, (uint32_t)k_steps, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 };
+// ---- packed records through a scalar row base (steps_quad_kernel: RockSample's loops, bound by vector-instruction issue) ----
+// QuadOut<Packed> / PairOut<Packed> with the address split in two: the row pointer is wave-uniform — the workgroup's first
+// record of the row, l0 less the thread's own lanes — and the thread's byte offset within the row a 32-bit constant of the
+// launch.  The store adds the two itself (the scalar-base form of global_store), and moving on to the next row is a scalar
+// add instead of a 64-bit vector add per step.  Two more scalar registers: the loops that have none to spare (Network's) keep
+// the plain sinks.
+static __device__ __forceinline__ uint32_t row_offset(uint32_t off)
+{
+    // the offset as the store sees it: an opaque 32-bit register at the store itself — widened to 64 bits once, outside the
+    // loop, it would be one half of a 64-bit vector add per step again
+    asm volatile("" : "+v"(off));
+    return off;
+}
+template <int LPT> struct PackedRowOut {
+    static_assert(LPT == 4 || LPT == 2, "a quad or half a quad per thread");
+    uint8_t *row;
+    uint32_t off;
+    int64_t pitch;                                          // bytes per row
+    __device__ __forceinline__ PackedRowOut(void *base, void *, void *, void *, int64_t rec_, uint32_t l0)
+        : row(reinterpret_cast<uint8_t *>(base) + 4ull * (l0 - (uint32_t)LPT * threadIdx.x)), off(4u * (uint32_t)LPT * threadIdx.x),
+          pitch(4 * rec_) {}
+    template <class Pol> __device__ __forceinline__ u32x4 first(const Pol &pol, int) { return pol.first(); }
+    __device__ __forceinline__ void put_records(const uint32_t (&r)[LPT], const uint32_t (&)[LPT])
+    {
+        off = row_offset(off);
+        if constexpr (LPT == 4) st_stream4(reinterpret_cast<uint32_t *>(row + off), r[0], r[1], r[2], r[3]);
+        else st_stream2(reinterpret_cast<uint32_t *>(row + off), r[0], r[1]);
+        row += pitch;
+    }
+    __device__ __forceinline__ void finish(int) {}
+};
+
 template <class L> struct pair_sink : std::false_type {};               // the sinks PairOut exists for
 template <> struct pair_sink<Packed> : std::true_type {};
 template <> struct pair_sink<Narrow> : std::true_type {};
 template <class Env> struct pair_sink<Returns<Env>> : std::true_type {};
-template <class L, int LPT> struct lanes_out { using type = QuadOut<L>; };
-template <class L> struct lanes_out<L, 2> { using type = PairOut<L>; };
+template <class L, int LPT, bool SROW = false> struct lanes_out { using type = QuadOut<L>; };   // SROW: packed records as PackedRowOut
+template <class L, bool SROW> struct lanes_out<L, 2, SROW> { using type = PairOut<L>; };
+template <> struct lanes_out<Packed, 4, true> { using type = PackedRowOut<4>; };
+template <> struct lanes_out<Packed, 2, true> { using type = PackedRowOut<2>; };
 
 // ---- a thread whose lanes are 256 apart (steps_kernel: lane j of a thread is base + tid + 256 j, j < LPT) ----------------
 // wg0: the workgroup's first lane within the shard (a multiple of 256); rel = tid + 256 j.  begin(j, rel): before the loop,

@@ -111,13 +111,15 @@ def blocks_of(lines):
             par = re.search(r"Parent Loop (BB\d+_\d+) Depth=(\d+)", note)
             cur = {"label": label, "header_depth": int(hdr.group(1)) if hdr else None,
                    "in_loop": (inl.group(1), int(inl.group(2))) if inl else None,
-                   "parent": (par.group(1), int(par.group(2))) if par else None, "insts": []}
+                   "parent": (par.group(1), int(par.group(2))) if par else None, "insts": [], "execnz_to": []}
             blocks.append(cur)
             i = j
             continue
         s = l.strip()
         if cur is not None and s and not s.startswith((";", ".", "#")):
             cur["insts"].append(s.split()[0])
+            if s.startswith("s_cbranch_execnz"):
+                cur["execnz_to"].append(s.split()[1])
         i += 1
     return blocks
 
@@ -127,11 +129,13 @@ def blocks_of(lines):
 PHILOX_OPS = ("v_mad_u64_u32", "v_mul_lo_u32", "v_mul_hi_u32", "v_bitop3_b32", "v_xor_b32")
 
 
-def is_tie_path(prev, b):
-    """An exec-masked block (the block before it ends in s_cbranch_execz, i.e. skips it when no lane takes it) that is
-    essentially one Philox block: the low-word block of a draw whose high word left the comparison undecided (2^-27 per
-    draw) — never on the common path, so it does not belong in the loop's mix."""
-    if prev is None or not prev["insts"] or prev["insts"][-1] != "s_cbranch_execz":
+def is_tie_path(prev, b, out_of_line=()):
+    """An exec-masked block (the block before it ends in s_cbranch_execz, i.e. skips it when no lane takes it; or, laid out
+    of line, it is where an s_cbranch_execnz goes when some lane takes it: `out_of_line`, those labels) that is essentially
+    one Philox block: the low-word block of a draw whose high word left the comparison undecided (2^-27 per draw) — never on
+    the common path, so it does not belong in the loop's mix."""
+    masked = prev is not None and prev["insts"] and prev["insts"][-1] == "s_cbranch_execz"
+    if not masked and b["label"] not in out_of_line:
         return False
     v = [i for i in b["insts"] if i.startswith("v_")]
     return len(v) >= 30 and sum(base(i) in PHILOX_OPS for i in v) >= 0.65 * len(v)
@@ -143,6 +147,7 @@ def hot_loop(blocks):
     -> (loop header, instructions of the common path, VALU instructions left out as tie paths)"""
     loops, cold = {}, {}
     prev = None
+    out_of_line = {t for b in blocks for t in b["execnz_to"]}
     for b in blocks:
         key = None
         if b["header_depth"] is not None:
@@ -150,7 +155,7 @@ def hot_loop(blocks):
         elif b["in_loop"]:
             key = b["in_loop"][0]
         if key:
-            if is_tie_path(prev, b):
+            if is_tie_path(prev, b, out_of_line):
                 cold[key] = cold.get(key, 0) + sum(i.startswith("v_") for i in b["insts"])
             else:
                 loops.setdefault(key, []).extend(b["insts"])
