@@ -204,16 +204,35 @@ struct RockEnv {
     // state words (one state word; ROT: in the rotated layout of build_rec_tab<true>) from the lanes' words R of the step's
     // sensor block; `start`: the start cell's position byte where the layout has it.  ONE branch for the ties; off it a lane
     // costs one v_and_or_b32 (ROT, `start` in a vector register) — the codes stay where the word has them.
-    template <int N, bool ROT>
+    // What sends a thread into the branch: rock j ties only if the word rotated right by 2 j + 2 lies in [2^31, 2^31 + 32),
+    // i.e. bits 2 j + 7 .. 2 j + 32 of the word, taken cyclically, are zero.  For every j < K those ranges share bits
+    // 2 K + 5 .. 31, so with 2 K + 5 < 32 a tie needs word < 2^(2 K + 5) = reset_tie_bound(K).  NUMERIC (the caller's choice
+    // per launch, for K <= RESET_NUMERIC_K): the filter is the smallest of the thread's words against `bound` (2^-11 per lane
+    // at K = 8) and no bit is counted off the branch.  Above, the bound passes too many lanes (one in 32 at K = 11) and the
+    // filter is the popcount test itself.
+    static constexpr int RESET_NUMERIC_K = 8;
+    static __device__ __forceinline__ uint32_t reset_tie_bound(int K) { return 1u << (2 * min(K, RESET_NUMERIC_K) + 5); }
+    template <int N, bool ROT, bool NUMERIC>
     static __device__ __forceinline__ void fresh_states(const uint32_t (&R)[N], const RngKey &key, uint32_t first, int K,
-                                                        uint32_t start, uint32_t (&fresh)[N])
+                                                        uint32_t start, uint32_t bound, uint32_t (&fresh)[N])
     {
         const uint32_t exist = K >= 16 ? 0xFFFFFFFFu : ((1u << (2 * K)) - 1u);
         auto word = [&](uint32_t codes) { return ROT ? (codes | start) : (start | (codes << 8)); };
-        int fewest = __popc(R[0]);
 #pragma unroll
-        for (int e = 0; e < N; ++e) { fresh[e] = word(R[e] & (0xAAAAAAAAu & exist)); fewest = min(fewest, (int)__popc(R[e])); }
-        if (fewest <= 6) {
+        for (int e = 0; e < N; ++e) fresh[e] = word(R[e] & (0xAAAAAAAAu & exist));
+        bool look;
+        if constexpr (NUMERIC) {
+            uint32_t least = R[0];
+#pragma unroll
+            for (int e = 1; e < N; ++e) least = min(least, R[e]);
+            look = least < bound;
+        } else {
+            int fewest = __popc(R[0]);
+#pragma unroll
+            for (int e = 1; e < N; ++e) fewest = min(fewest, (int)__popc(R[e]));
+            look = fewest <= 6;
+        }
+        if (look) {
 #pragma unroll
             for (int e = 0; e < N; ++e)
                 if (__popc(R[e]) <= 6) reset_ties<true>(R[e], key, first + (uint32_t)e, K, fresh[e], ROT ? 0 : 8);
@@ -481,6 +500,7 @@ struct RockEnv {
     // (traj_out.hip.h: action | ob << 8 | reward code << 16 | done << 24) and its new state in 20 with one state word (measured
     // in the quad loop's gfx950 code; 27 until the entry held the record's bytes), from a table whose entries already hold, per
     // (action, position), everything that does not depend on the rocks' codes:
+    // Two state words (4-byte entries):
     //   every entry: bits 28-30 = the OUTCOME CODE the step has when no uncollected rock is sampled ("fallback"), bit 31 =
     //                a rock with an id < K lies under a SAMPLE;
     //   a <  4: bits 0-7 = position byte XOR new position byte (0 if the move leaves); fallback 6 inside, 3 leaving east,
@@ -495,7 +515,16 @@ struct RockEnv {
     // Outcome codes: 0 = bad rock sampled (-10), 1 = penalty (-100, done), 2 = good rock sampled (+10), 3 = east exit (+10,
     // done), 6 = nothing (0) — a sampled rock's own code IS its outcome code, done is bit 0.
     // One state word (K <= 12): the entry is 8 bytes, read with one ds_read_b64 (17 x 256 x 8 = 34 KB of LDS per workgroup,
-    // four workgroups per CU fit).  The second word is the fallback's record in its final place, and where the state changes:
+    // four workgroups per CU fit).  The first word is what the lane's RAW sensor word H compares with:
+    //   a >= 5: E = T << 5 with T = thr >> 26 the threshold's high part at this distance, saturated to 0xFFFFFFFF where
+    //           T = 2^27 (a sensor that is always right at distance 0).  `correct` = H < E is (H >> 5) < T exactly for every
+    //           T < 2^27, and the draw the high word leaves undecided, (H >> 5) == T, is H - E < 32 (unsigned);
+    //   a <  5: 0xFFFFFFFF (`correct` is not used).
+    // H - E < 32 is a FILTER: against a saturated or a non-CHECK entry it also passes H = 0xFFFFFFFF and, wrapping, H < 31
+    // (2^-27 per lane-step); the rare path behind it (rec_sensor_exact) recomputes the draw from the threshold itself,
+    // (H >> 5) against T and the low word on equality.
+    // The second word is the fallback's record in its final place, and where the state changes:
+    //   bit 31     = a rock with an id < K lies under a SAMPLE (REC_ROCK; rec_finish masks it out of the record);
     //   bits 16-23 = the fallback's reward byte, bit 24 = its done bit: the record's upper half as it is stored;
     //   bits 8-9   = 3 in a CHECK's entry, else 0: the record's ob field keeps bit 9 if the reading matches the rock, else
     //                bit 8 (one select between two masks, one v_and_or_b32 that also puts the action in);
@@ -507,17 +536,22 @@ struct RockEnv {
     //                offset, and its record is 0x00F60004 - q * 0x00760000 (reward byte 0xF6 = -10 or 0x0A = +10, action 4).
     // done is read off the finished record (>= 1 << 24).
     // The quad-per-thread loops (steps_quad_kernel) take the step in its two halves — rec_lookup for all of a thread's lanes, one
-    // wait, the compares, ONE branch for the lanes whose draw ties, rec_finish — and keep the state word rotated right by 8 in
+    // wait, one v_sub_co_u32 per lane (H - e for the filter; its borrow IS `correct`), ONE branch for the lanes the filter passes,
+    // rec_finish — and keep the state word rotated right by 8 in
     // registers (ROT: rock j's code at bit 2 j, the position byte on top; one v_alignbit_b32 per lane after the launch's load
     // and one before its store): the entry's address is one v_alignbit_b32 and one v_and_b32 (a << 11 | position << 3), and a
     // fresh episode one v_and_or_b32 of the lane's sensor word — its rocks' codes are where the word has them — instead of a
-    // v_and_b32 and a v_lshl_or_b32: 19 + 1 vector instructions per lane-step there.  The table differs in its bit offsets only
-    // (build_rec_tab<true>).
+    // v_and_b32 and a v_lshl_or_b32: 17 + 1 vector instructions per lane-step there and three per thread for the filter
+    // (v_min_u32, v_min3_u32, one compare).  The table differs in its bit offsets only (build_rec_tab<true>).
     // Two state words keep 4-byte entries (21 x 256 x 8 = 42 KB would leave three workgroups per CU), test the action, and
     // look the reward byte up by outcome code with one v_perm_b32 in an 8-byte constant; that branch is as it was.
     static constexpr uint32_t REC_LUT_LO = 0x0A0A9CF6u, REC_LUT_HI = 0x00000000u;   // reward byte by outcome code 0..7 (two state words)
     using TabEntry = typename std::conditional<W == 1, uint2, uint32_t>::type;
     struct RecTab { TabEntry e[TAB_ACTIONS][256]; };
+    static constexpr uint32_t REC_ROCK = 1u << 31;           // second word of a one-state-word entry: a rock lies under this SAMPLE
+    static constexpr uint32_t TIE_SPAN = 32u;                // H - E below this: the high word may leave the draw undecided
+    // first word of a one-state-word CHECK entry from the threshold's high part T = thr >> 26 <= 2^27
+    static __device__ __forceinline__ uint32_t rec_thr_word(uint32_t T) { return T >= (1u << 27) ? 0xFFFFFFFFu : T << 5; }
     // second word of a one-state-word entry: step `c` (-1, 0, +1) at bit offset `off`, ob mask, the record's reward byte and done bit
     static __device__ __forceinline__ uint32_t rec_f(uint32_t off, int c, uint32_t ob_mask, uint32_t oc)
     {
@@ -538,7 +572,7 @@ struct RockEnv {
         const uint32_t x = (uint32_t)pos & 15u, y = (uint32_t)pos >> 4, size = (uint32_t)p.size, K = (uint32_t)p.num_rocks;
         const int id = sh.grid[x * 16 + y];
         const uint32_t NOTHING = 6u << 28, PENALTY = (STOCH ? 6u : 1u) << 28, EXIT_EAST = 3u << 28;
-        const uint32_t NO_TIE = 1u << 27;
+        const uint32_t NO_TIE = 1u << 27;                                        // (two state words)
         for (int a = 0; a < 5 + (int)K && a < TAB_ACTIONS; ++a) {
             uint32_t e, f;
             if (a < 4) {
@@ -556,7 +590,7 @@ struct RockEnv {
                 e = sh.thr[__builtin_amdgcn_sad_u8(x | (y << 8), sh.rpos[a - 5], 0u) & 31u].x | NOTHING;
                 f = rec_f(ROCK0 + 2u * (uint32_t)(a - 5), 0, 3u, 6u);
             }
-            if constexpr (W == 1) tab.e[a][pos] = make_uint2(e, f);
+            if constexpr (W == 1) tab.e[a][pos] = make_uint2(a > 4 ? rec_thr_word(e & ~NOTHING) : 0xFFFFFFFFu, f | (a == 4 ? e & REC_ROCK : 0u));
             else tab.e[a][pos] = e;
         }
     }
@@ -565,9 +599,9 @@ struct RockEnv {
     // codes run on into the upper word (rock j at bits 8 + 2 j), a code never straddles the words, and the word a SAMPLE or
     // a CHECK reads is a select on bit 5 of its bit offset.
     // The one-state-word lane step in its two halves, for the loops that issue the table reads of all of a thread's lanes before
-    // they use the first (steps_quad_kernel): rec_lookup reads the entry, rec_kh is what the entry's first word compares with
-    // (`correct` = rec_kh(H) < e, a tie = rec_kh(H) == e: then the low word decides, against rec_thr_lo), rec_finish makes the
-    // record and the new state.  ROT: the state word is kept rotated (build_rec_tab<true>).
+    // they use the first (steps_quad_kernel): rec_lookup reads the entry, the raw sensor word compares with its first word
+    // (`correct` = H < e; H - e < TIE_SPAN: rec_sensor_exact decides instead), rec_finish makes the record and the new state.
+    // ROT: the state word is kept rotated (build_rec_tab<true>).
     template <bool ROT = false>
     static __device__ __forceinline__ uint2 rec_lookup(const RecTab &tab, uint32_t s, uint32_t a)
     {
@@ -578,25 +612,33 @@ struct RockEnv {
             return *reinterpret_cast<const uint2 *>(reinterpret_cast<const char *>(&tab.e[0][0]) + off);
         } else return tab.e[a][s & 0xFFu];
     }
-    static __device__ __forceinline__ uint32_t rec_kh(uint32_t H) { return __builtin_amdgcn_alignbit(12u, H, 5u); }   // (H >> 5) | 6 << 28
-    // (ROT: the measured rock is read off the entry — its offset is 2 (a - 5) — so that a tape-driven loop's rare path does not
-    // keep the action, i.e. a tape row it wants to load over, alive)
-    template <bool ROT = false>
-    static __device__ __forceinline__ uint32_t rec_thr_lo(const Shared &sh, uint32_t s, uint32_t a, uint32_t f)
+    // The sensor draw of a lane the filter H - e < TIE_SPAN passed, from the threshold itself: (H >> 5) against T, the low word
+    // against the threshold's low 26 bits where they are equal (2^-27 per CHECK).  The measured rock is read off the entry's
+    // offset, not the action, so that a tape-driven loop's rare path does not keep a tape row it wants to load over alive.  The
+    // filter also passes H = 0xFFFFFFFF and H < 31 on a move or a SAMPLE: their offsets name some rock slot below 16, every
+    // read stays inside its table, and rec_finish does not use `correct` for them.
+    template <bool ROT = false, class LowWord>
+    static __device__ __forceinline__ bool rec_sensor_exact(const Shared &sh, uint32_t s, uint32_t f, uint32_t H, LowWord lo)
     {
-        if constexpr (ROT) return thr_lo_of(sh, State{(S)(s >> ROT_POS)}, (int)((f & 31u) >> 1));
-        else return thr_lo_of(sh, State{(S)s}, (int)a - 5);
+        const uint32_t pos = ROT ? s >> ROT_POS : s, r = (((f & 31u) - (ROT ? 0u : 8u)) >> 1) & 15u;
+        const uint2 t = sh.thr[__builtin_amdgcn_sad_u8((pos & 15u) | ((pos & 0xF0u) << 4), sh.rpos[r], 0u) & 31u];
+        // (the low word is drawn whatever the comparison says — all but 2^-5 of the lanes that come here need it — and pinned
+        // before the comparison, so that the rare path is one straight block)
+        const uint32_t kh = H >> 5;
+        uint32_t kl = lo() >> 6;
+        asm volatile("" : "+v"(kl));
+        return kh == t.x ? kl <= t.y : kh < t.x;
     }
     static __device__ __forceinline__ void rec_finish(const uint2 ef, uint32_t &s, uint32_t a, bool correct, uint32_t fresh, uint32_t &rec)
     {
-        const uint32_t e = ef.x, f = ef.y;
+        const uint32_t f = ef.y;
         // the code of the rock this step is about — under a SAMPLE, or the one a CHECK measures — read at the entry's offset
         // (a move's entry points at the position nibble it changes: whatever this reads there is not used)
         const uint32_t q = __builtin_amdgcn_ubfe(s, f, 2u);
-        const bool ok = ((int32_t)e < 0) & (q != 1u);                       // SAMPLE: an uncollected rock with an id < K is underfoot
-        // the record when no live rock is sampled: the entry's own bytes, of its two ob bits the one the reading gives
-        // (CHECK rock a - 5, rock.py:171-175, 401-407: good = its code is 2)
-        const uint32_t keep = ((q == 2u) == correct) ? 0xFFFFFE00u : 0xFFFFFD00u;
+        const bool ok = ((int32_t)f < 0) & (q != 1u);                       // SAMPLE: an uncollected rock with an id < K is underfoot (REC_ROCK)
+        // the record when no live rock is sampled: the entry's own bytes without REC_ROCK, of its two ob bits the one the
+        // reading gives (CHECK rock a - 5, rock.py:171-175, 401-407: good = its code is 2)
+        const uint32_t keep = ((q == 2u) == correct) ? 0x7FFFFE00u : 0x7FFFFD00u;
         const uint32_t rfb = (f & keep) | a;
         // a sampled rock's code IS its outcome: 0 -> -10 (0xF6), 2 -> +10 (0x0A), never done; the action byte is SAMPLE's
         const uint32_t rok = 0x00F60004u - q * 0x00760000u;
@@ -613,9 +655,8 @@ struct RockEnv {
         const uint32_t s_lo = (uint32_t)s, s_hi = W == 2 ? (uint32_t)((uint64_t)s >> 32) : 0u;
         if constexpr (W == 1) {
             const uint2 ef = rec_lookup(tab, s_lo, a);
-            const uint32_t kh = rec_kh(H);                                      // compares with the entry itself
-            bool correct = kh < ef.x;
-            if (kh == ef.x) correct = (lo() >> 6) <= rec_thr_lo(sh, s_lo, a, ef.y);   // a CHECK only (NO_TIE); probability 2^-27
+            bool correct = H < ef.x;                                            // the raw word against the entry itself
+            if (H - ef.x < TIE_SPAN) correct = rec_sensor_exact(sh, s_lo, ef.y, H, lo);   // 2^-27 per CHECK
             uint32_t sn = s_lo;
             rec_finish(ef, sn, a, correct, (uint32_t)fresh, rec);
             s = (S)sn;

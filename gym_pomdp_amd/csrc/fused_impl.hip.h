@@ -368,12 +368,14 @@ __global__ __launch_bounds__(BLOCK) void steps_kernel(uint32_t *__restrict__ sta
 // (pair_shared: thread e computes the block of step s + e at every even s, two DPP moves swap the halves): one block of each
 // stream per thread per two steps — as many per lane-step as with a quad per thread — and twice the waves.  4-byte sinks and
 // the returns sink (PairOut).
-template <class Env, class L = Columns, class Pol = SyntheticQuad, int LPT = 4>
-__global__ __launch_bounds__(BLOCK) void steps_quad_kernel(uint32_t *__restrict__ state, int32_t *__restrict__ action,
-                                                           int32_t *__restrict__ ob, int32_t *__restrict__ reward,
-                                                           uint8_t *__restrict__ done, int64_t n, RngKey key0, uint32_t lane0,
-                                                           RngKey akey0, int k_steps, int64_t rec, int gen_first,
-                                                           const typename Env::Params p, TapeRef tape)
+// NUMERIC (one state word): which filter sends a thread to look for reset ties, RockEnv::fresh_states — by number up to
+// RockEnv::RESET_NUMERIC_K rocks (steps_quad_kernel), by popcount above (steps_quad_popc_kernel); the launcher picks by the board.
+template <class Env, class L, class Pol, int LPT, bool NUMERIC>
+__device__ __forceinline__ void steps_quad_body(uint32_t *__restrict__ state, int32_t *__restrict__ action,
+                                                int32_t *__restrict__ ob, int32_t *__restrict__ reward,
+                                                uint8_t *__restrict__ done, int64_t n, RngKey key0, uint32_t lane0,
+                                                RngKey akey0, int k_steps, int64_t rec, int gen_first,
+                                                const typename Env::Params &p, TapeRef tape)
 {
     static_assert(LPT == 4 || LPT == 2, "a quad or half a quad per thread");
     constexpr int W = Env::WORDS;
@@ -382,7 +384,7 @@ __global__ __launch_bounds__(BLOCK) void steps_quad_kernel(uint32_t *__restrict_
     constexpr bool ROT = W == 1;
     using S = typename Env::S;
     __shared__ typename Env::Shared sh;
-    // the lane step yields the lane's packed record straight from RecTab (one state word: RockEnv::rec_lookup / rec_finish, 19
+    // the lane step yields the lane's packed record straight from RecTab (one state word: RockEnv::rec_lookup / rec_finish, 17
     // vector instructions per lane-step and one for the fresh episode it may need; two: RockEnv::step_rec)
     __shared__ typename Env::RecTab tab;
     const uint32_t n_act = (uint32_t)Env::n_actions(p);
@@ -432,6 +434,9 @@ __global__ __launch_bounds__(BLOCK) void steps_quad_kernel(uint32_t *__restrict_
     // a quad per thread: the quad's STEP blocks have counter words 0 and 3 fixed for the launch (philox4x32_10_fixed)
     const PhiloxFixed sensor_fx = philox_fixed(glane0 >> 2, ((uint32_t)POMDP_STREAM_STEP << 24) | SENSOR_BLOCK, key0.k1);
     const PhiloxFixed gate_fx = philox_fixed(glane0 >> 2, (uint32_t)POMDP_STREAM_STEP << 24, key0.k1);
+    // the bound of the numeric reset-tie filter, RockEnv::fresh_states, in a scalar register
+    uint32_t tie_bound = 0;
+    if constexpr (ROT && NUMERIC) { tie_bound = Env::reset_tie_bound(K); asm volatile("" : "+s"(tie_bound)); }
     auto step_body = [&](const int s, const auto par_) __attribute__((always_inline)) {
         constexpr int PAR = decltype(par_)::value;           // AHEAD2: s & 1
         const RngKey key = cx.key(key0, s);
@@ -474,27 +479,36 @@ __global__ __launch_bounds__(BLOCK) void steps_quad_kernel(uint32_t *__restrict_
             return Env::elem(Env::quad_block(rare_key(key), glane0 + (uint32_t)j, SENSOR_BLOCK + 1u), e0 + (uint32_t)j);
         };
         if constexpr (ROT) {
-            // the lane step in two phases: every table read of the thread first — one wait for all of them — then every
-            // compare, ONE branch for the lanes whose sensor draw the high word leaves undecided (2^-27 per CHECK), then the records
-            uint32_t fresh[LPT], kh[LPT], sn[LPT];
+            // the lane step in two phases: every table read of the thread first — one wait for all of them — then ONE branch
+            // for the lanes whose sensor draw the high word may leave undecided (H - e < TIE_SPAN; 2^-27 per CHECK), then every
+            // compare and the records
+            uint32_t fresh[LPT], sn[LPT];
             uint2 ef[LPT];
-            bool correct[LPT], tie[LPT], any_tie = false;
-            Env::template fresh_states<LPT, true>(H, key, glane0, K, start_rot, fresh);
+            Env::template fresh_states<LPT, true, NUMERIC>(H, key, glane0, K, start_rot, tie_bound, fresh);
 #pragma unroll
             for (int j = 0; j < LPT; ++j) ef[j] = Env::template rec_lookup<true>(tab, st[j].s, valid[j] ? a_taken[j] : 0u);
-            if constexpr (LPT == 4) asm volatile("" : "+v"(ef[0].x), "+v"(ef[0].y), "+v"(ef[1].x), "+v"(ef[1].y), "+v"(ef[2].x), "+v"(ef[2].y), "+v"(ef[3].x), "+v"(ef[3].y));
-            else asm volatile("" : "+v"(ef[0].x), "+v"(ef[0].y), "+v"(ef[1].x), "+v"(ef[1].y));   // all of them have landed: one wait
+            {   // all of them have landed: one wait (each entry passes as the register pair its read filled: no copies)
+                uint64_t w[LPT];
 #pragma unroll
-            for (int j = 0; j < LPT; ++j) {
-                kh[j] = Env::rec_kh(H[j]);
-                correct[j] = kh[j] < ef[j].x;
-                tie[j] = kh[j] == ef[j].x;                                   // a CHECK only (NO_TIE)
-                any_tie |= tie[j];
+                for (int j = 0; j < LPT; ++j) w[j] = (uint64_t)ef[j].x | ((uint64_t)ef[j].y << 32);
+                if constexpr (LPT == 4) asm volatile("" : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]));
+                else asm volatile("" : "+v"(w[0]), "+v"(w[1]));
+#pragma unroll
+                for (int j = 0; j < LPT; ++j) ef[j] = make_uint2((uint32_t)w[j], (uint32_t)(w[j] >> 32));
             }
-            if (any_tie) {
+            // H - e with its borrow: the borrow IS `correct` = H < e, the difference feeds the filter (one v_sub_co_u32 per lane)
+            uint32_t near[LPT];
+            bool correct[LPT];
+#pragma unroll
+            for (int j = 0; j < LPT; ++j) correct[j] = __builtin_sub_overflow(H[j], ef[j].x, &near[j]);
+            uint32_t nearest = near[0];
+#pragma unroll
+            for (int j = 1; j < LPT; ++j) nearest = min(nearest, near[j]);
+            if (nearest < Env::TIE_SPAN) {
 #pragma unroll
                 for (int j = 0; j < LPT; ++j)
-                    if (tie[j]) correct[j] = (low_word(j) >> 6) <= Env::template rec_thr_lo<true>(sh, st[j].s, a_taken[j], ef[j].y);
+                    if (near[j] < Env::TIE_SPAN)
+                        correct[j] = Env::template rec_sensor_exact<true>(sh, st[j].s, ef[j].y, H[j], [&]() { return low_word(j); });
             }
 #pragma unroll
             for (int j = 0; j < LPT; ++j) {
@@ -569,6 +583,26 @@ __global__ __launch_bounds__(BLOCK) void steps_quad_kernel(uint32_t *__restrict_
         st_stream2(state + l0, w_lo[0], w_lo[1]);
         if (W == 2) st_stream2(state + n + l0, (uint32_t)((uint64_t)st[0].s >> 32), (uint32_t)((uint64_t)st[1].s >> 32));
     }
+}
+template <class Env, class L = Columns, class Pol = SyntheticQuad, int LPT = 4>
+__global__ __launch_bounds__(BLOCK) void steps_quad_kernel(uint32_t *__restrict__ state, int32_t *__restrict__ action,
+                                                           int32_t *__restrict__ ob, int32_t *__restrict__ reward,
+                                                           uint8_t *__restrict__ done, int64_t n, RngKey key0, uint32_t lane0,
+                                                           RngKey akey0, int k_steps, int64_t rec, int gen_first,
+                                                           const typename Env::Params p, TapeRef tape)
+{
+    steps_quad_body<Env, L, Pol, LPT, Env::WORDS == 1>(state, action, ob, reward, done, n, key0, lane0, akey0, k_steps, rec, gen_first, p, tape);
+}
+// ... for the one-state-word boards with more than RockEnv::RESET_NUMERIC_K rocks
+template <class Env, class L = Columns, class Pol = SyntheticQuad, int LPT = 4>
+__global__ __launch_bounds__(BLOCK) void steps_quad_popc_kernel(uint32_t *__restrict__ state, int32_t *__restrict__ action,
+                                                                int32_t *__restrict__ ob, int32_t *__restrict__ reward,
+                                                                uint8_t *__restrict__ done, int64_t n, RngKey key0, uint32_t lane0,
+                                                                RngKey akey0, int k_steps, int64_t rec, int gen_first,
+                                                                const typename Env::Params p, TapeRef tape)
+{
+    static_assert(Env::WORDS == 1, "two state words take reset_codes4");
+    steps_quad_body<Env, L, Pol, LPT, false>(state, action, ob, reward, done, n, key0, lane0, akey0, k_steps, rec, gen_first, p, tape);
 }
 
 // Tag (one opponent) with a quad per thread: the policy's ACTION block is the thread's own, and so is the quad's STEP block —
@@ -1352,15 +1386,20 @@ static int launch_steps_fused_l(const typename Env::Params &p, uint32_t *state, 
                 char pname[40];
                 snprintf(pname, sizeof pname, "%s, 2", lname);
                 note_fused("steps_quad_kernel", Env::NAME, pname);
-                const dim3 pgrid((unsigned)(n / (2 * BLOCK)));
-                if (taped) hipLaunchKernelGGL((steps_quad_kernel<Env, L, TapeQuad, 2>), pgrid, dim3(BLOCK), 0, (hipStream_t)stream, POMDP_QUAD_ARGS);
-                else hipLaunchKernelGGL((steps_quad_kernel<Env, L, SyntheticQuad, 2>), pgrid, dim3(BLOCK), 0, (hipStream_t)stream, POMDP_QUAD_ARGS);
+                // (one state word: the reset-tie filter by number or by popcount, RockEnv::fresh_states — the same loop otherwise)
+                bool popc = false;
+                if constexpr (Env::WORDS == 1) popc = p.num_rocks > Env::RESET_NUMERIC_K;
+                if constexpr (Env::WORDS == 1) { if (popc) POMDP_LAUNCH_PAIR(steps_quad_popc_kernel<Env, L); }
+                if (!popc) POMDP_LAUNCH_PAIR(steps_quad_kernel<Env, L);
                 launched = true;
             }
         }
         if (!launched && quad_ok && n >= (Env::STOCHASTIC ? QUAD_MIN_STOCHROCK : QUAD_MIN_ROCK) && k >= 16 && p.num_rocks + 5 <= Env::TAB_ACTIONS) {
             note_fused("steps_quad_kernel", Env::NAME, lname);
-            POMDP_LAUNCH_QUAD(steps_quad_kernel<Env, L);
+            bool popc = false;
+            if constexpr (Env::WORDS == 1) popc = p.num_rocks > Env::RESET_NUMERIC_K;
+            if constexpr (Env::WORDS == 1) { if (popc) POMDP_LAUNCH_QUAD(steps_quad_popc_kernel<Env, L); }
+            if (!popc) POMDP_LAUNCH_QUAD(steps_quad_kernel<Env, L);
             launched = true;
         }
     }

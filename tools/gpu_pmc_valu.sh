@@ -101,5 +101,6 @@ for set in $SETS; do
   esac
 done
 cd $REPO
-python tools/pmc_valu_summary.py $W $OUT "$(ls -t profiles/*_pmc_valu.json 2>/dev/null | head -1)"
+# (the newest by name — round tags sort — never by mtime, which a fresh checkout scrambles: bench.py _latest)
+python tools/pmc_valu_summary.py $W $OUT "$(ls profiles/*_pmc_valu.json 2>/dev/null | sort | tail -1)"
 ls -la $OUT

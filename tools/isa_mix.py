@@ -23,7 +23,7 @@ import sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(REPO, "gym_pomdp_amd", "csrc")
 UNITS = ["fused_rock.hip", "fused_tag.hip", "fused_battleship.hip", "fused_misc.hip", "planner.hip"]   # where the kernels of interest live
-DEFAULT = ["steps_quad_kernel<pomdp::RockEnv<1, false>, ", "steps_quad_kernel<pomdp::RockEnv<2, false>, ", "rollout_kernel<pomdp::RockEnv<2, false>",
+DEFAULT = ["steps_quad_kernel<pomdp::RockEnv<1, false>, ", "steps_quad_popc_kernel<pomdp::RockEnv<1, false>, ", "steps_quad_kernel<pomdp::RockEnv<2, false>, ", "rollout_kernel<pomdp::RockEnv<2, false>",
            "rollout_kernel<pomdp::RockEnv<1, false>", "rollout_kernel<pomdp::TagEnv", "heuristic_steps_kernel<pomdp::RockEnv<1, false>, false",
            "heuristic_steps_kernel<pomdp::RockEnv<2, false>, false", "heuristic_steps_kernel<pomdp::TagEnv, false",
            "tag_steps_quad_kernel<true, ", "network_steps_quad_kernel<2, ", "steps_quad_generic_kernel<pomdp::TigerEnv, ",
@@ -58,8 +58,8 @@ def assembly(path=None):
     def one(u):
         out = os.path.join(d, u + ".s")
         src = os.path.join(CSRC, u)
-        if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(os.path.join(CSRC, f)) for f in os.listdir(CSRC)
-                                                                  if f.endswith((".hip", ".h"))):
+        if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(os.path.join(r, f)) for r, _, fs in os.walk(CSRC)
+                                                                  for f in fs if f.endswith((".hip", ".h"))):
             subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
                                    "--cuda-device-only", "-S", "-o", out, src], stderr=subprocess.DEVNULL)
         return open(out).read()
@@ -111,7 +111,7 @@ def blocks_of(lines):
             par = re.search(r"Parent Loop (BB\d+_\d+) Depth=(\d+)", note)
             cur = {"label": label, "header_depth": int(hdr.group(1)) if hdr else None,
                    "in_loop": (inl.group(1), int(inl.group(2))) if inl else None,
-                   "parent": (par.group(1), int(par.group(2))) if par else None, "insts": [], "execnz_to": []}
+                   "parent": (par.group(1), int(par.group(2))) if par else None, "insts": [], "execnz_to": [], "branches": []}
             blocks.append(cur)
             i = j
             continue
@@ -120,6 +120,8 @@ def blocks_of(lines):
             cur["insts"].append(s.split()[0])
             if s.startswith("s_cbranch_execnz"):
                 cur["execnz_to"].append(s.split()[1])
+            if s.startswith(("s_cbranch_", "s_branch")):
+                cur["branches"].append((s.split()[0], s.split()[1]))
         i += 1
     return blocks
 
@@ -138,7 +140,62 @@ def is_tie_path(prev, b, out_of_line=()):
     if not masked and b["label"] not in out_of_line:
         return False
     v = [i for i in b["insts"] if i.startswith("v_")]
-    return len(v) >= 30 and sum(base(i) in PHILOX_OPS for i in v) >= 0.65 * len(v)
+    return len(v) >= 30 and sum(base(i) in PHILOX_OPS for i in v) >= 0.6 * len(v)
+
+
+def loop_key(b):
+    if b["header_depth"] is not None:
+        return b["label"].lstrip(".L")
+    return b["in_loop"][0] if b["in_loop"] else None
+
+
+def rare_regions(blocks, ties):
+    """The blocks that share an exec-masked region with a tie path of their own loop: the lead-in of a draw the high word
+    leaves undecided (the filter's per-lane test, the threshold's lookup, the comparison) and the code that puts its outcome
+    back.  A masked edge is what runs only when some lane asks for it — inside a loop, the fall-through of a block that ends
+    in s_cbranch_execz, the target of an s_cbranch_execnz; a block no other edge reaches from the kernel's entry is masked, and
+    the masked blocks that hang together (through the loops nested among them too) are one region.  A region is left out with
+    the tie path of the SAME loop it holds if what guards it is a thread's one filter over all its lanes — the block it is
+    entered from takes the smallest of the lanes' distances to their thresholds (v_min_u32 / v_min3_u32) and tests that: the
+    quad loops' form since the lane step compares the raw sensor word.  Every other masked block stays in the mix as it always
+    did: a region that only leads to nested loops (the reset ties' per-rock loops), a lane's own tie test, a continuation
+    pass.  `ties`: indices of the tie-path blocks.  -> indices of the blocks left out"""
+    at = {b["label"]: i for i, b in enumerate(blocks)}
+    common, masked_e = {}, {}
+    for i, b in enumerate(blocks):
+        c, m = [], []
+        inside = loop_key(b) is not None                   # (outside every loop: the kernel's own range guards, common to all)
+        for mn, t in b["branches"]:
+            if t in at:
+                (m if inside and mn == "s_cbranch_execnz" else c).append(at[t])
+        last = b["insts"][-1] if b["insts"] else None
+        if last not in ("s_branch", "s_endpgm") and i + 1 < len(blocks):
+            (m if inside and last == "s_cbranch_execz" else c).append(i + 1)
+        common[i], masked_e[i] = c, m
+    seen, todo = {0}, [0]
+    while todo:
+        for j in common[todo.pop()]:
+            if j not in seen:
+                seen.add(j)
+                todo.append(j)
+    out, done = set(), set()
+    for i in range(len(blocks)):
+        if i in seen or i in done:
+            continue
+        region, todo = {i}, [i]
+        while todo:
+            k = todo.pop()
+            for j in common[k] + masked_e[k] + [p for p in range(len(blocks)) if p not in seen and k in common[p] + masked_e[p]]:
+                if j not in seen and j not in region:
+                    region.add(j)
+                    todo.append(j)
+        done |= region
+        guards = [p for p in seen if any(j in region for j in masked_e[p])]
+        if not any(base(mn) in ("v_min_u32", "v_min3_u32") for p in guards for mn in blocks[p]["insts"]):
+            continue
+        keys = {loop_key(blocks[t]) for t in region if t in ties}
+        out |= {j for j in region if loop_key(blocks[j]) in keys}
+    return out
 
 
 def hot_loop(blocks):
@@ -146,20 +203,16 @@ def hot_loop(blocks):
     instructions in its OWN blocks; the loops nested inside it and tie-path blocks left out.
     -> (loop header, instructions of the common path, VALU instructions left out as tie paths)"""
     loops, cold = {}, {}
-    prev = None
     out_of_line = {t for b in blocks for t in b["execnz_to"]}
-    for b in blocks:
-        key = None
-        if b["header_depth"] is not None:
-            key = b["label"].lstrip(".L")
-        elif b["in_loop"]:
-            key = b["in_loop"][0]
+    ties = {i for i, b in enumerate(blocks) if loop_key(b) and is_tie_path(blocks[i - 1] if i else None, b, out_of_line)}
+    rare = ties | rare_regions(blocks, ties)
+    for i, b in enumerate(blocks):
+        key = loop_key(b)
         if key:
-            if is_tie_path(prev, b, out_of_line):
+            if i in rare:
                 cold[key] = cold.get(key, 0) + sum(i.startswith("v_") for i in b["insts"])
             else:
                 loops.setdefault(key, []).extend(b["insts"])
-        prev = b
     if not loops:
         return None, [], 0
     key = max(loops, key=lambda k: len(loops[k]))
