@@ -210,16 +210,24 @@ struct RockEnv {
     // per launch, for K <= RESET_NUMERIC_K): the filter is the smallest of the thread's words against `bound` (2^-11 per lane
     // at K = 8) and no bit is counted off the branch.  Above, the bound passes too many lanes (one in 32 at K = 11) and the
     // filter is the popcount test itself.
+    // INS (with ROT, K <= RESET_NUMERIC_K): the layout of build_rec_tab<true, true>, rock 0's code at bit INS_ROCK0 — the word
+    // shifted up by that, then the same v_and_or_b32.
     static constexpr int RESET_NUMERIC_K = 8;
+    static constexpr uint32_t INS_ROCK0 = 5u;
     static __device__ __forceinline__ uint32_t reset_tie_bound(int K) { return 1u << (2 * min(K, RESET_NUMERIC_K) + 5); }
-    template <int N, bool ROT, bool NUMERIC>
+    template <int N, bool ROT, bool NUMERIC, bool INS = false>
     static __device__ __forceinline__ void fresh_states(const uint32_t (&R)[N], const RngKey &key, uint32_t first, int K,
                                                         uint32_t start, uint32_t bound, uint32_t (&fresh)[N])
     {
+        static_assert(!INS || (ROT && NUMERIC), "the insert layout is the rotated one of the boards with at most RESET_NUMERIC_K rocks");
         const uint32_t exist = K >= 16 ? 0xFFFFFFFFu : ((1u << (2 * K)) - 1u);
+        constexpr int ROCK0 = INS ? (int)INS_ROCK0 : ROT ? 0 : 8;
         auto word = [&](uint32_t codes) { return ROT ? (codes | start) : (start | (codes << 8)); };
 #pragma unroll
-        for (int e = 0; e < N; ++e) fresh[e] = word(R[e] & (0xAAAAAAAAu & exist));
+        for (int e = 0; e < N; ++e) {
+            if constexpr (INS) fresh[e] = ((R[e] << INS_ROCK0) & ((0xAAAAAAAAu & exist) << INS_ROCK0)) | start;
+            else fresh[e] = word(R[e] & (0xAAAAAAAAu & exist));
+        }
         bool look;
         if constexpr (NUMERIC) {
             uint32_t least = R[0];
@@ -235,7 +243,7 @@ struct RockEnv {
         if (look) {
 #pragma unroll
             for (int e = 0; e < N; ++e)
-                if (__popc(R[e]) <= 6) reset_ties<true>(R[e], key, first + (uint32_t)e, K, fresh[e], ROT ? 0 : 8);
+                if (__popc(R[e]) <= 6) reset_ties<true>(R[e], key, first + (uint32_t)e, K, fresh[e], ROCK0);
         }
     }
     // rock.py:236-241 reset -> 266-271 _get_init_state -> 78-86 Rock.__init__:
@@ -543,6 +551,10 @@ struct RockEnv {
     // fresh episode one v_and_or_b32 of the lane's sensor word — its rocks' codes are where the word has them — instead of a
     // v_and_b32 and a v_lshl_or_b32: 17 + 1 vector instructions per lane-step there and three per thread for the filter
     // (v_min_u32, v_min3_u32, one compare).  The table differs in its bit offsets only (build_rec_tab<true>).
+    // With at most RESET_NUMERIC_K = 8 rocks (INS, steps_quad_kernel; build_rec_tab<true, true> below) the codes sit five bits
+    // higher and the state half of the step is one masked insert of the entry's first word: the v_sub_u32, v_bfe_i32,
+    // v_cndmask_b32 and v_lshl_add_u32 of the step form become a v_bfm_b32 and a v_bfi_b32, the address loses its v_and_b32 and
+    // the fresh episode gains a v_lshlrev_b32 — 15 + 1 per lane-step.  steps_quad_popc_kernel (9 to 12 rocks) keeps 17 + 1.
     // Two state words keep 4-byte entries (21 x 256 x 8 = 42 KB would leave three workgroups per CU), test the action, and
     // look the reward byte up by outcome code with one v_perm_b32 in an 8-byte constant; that branch is as it was.
     static constexpr uint32_t REC_LUT_LO = 0x0A0A9CF6u, REC_LUT_HI = 0x00000000u;   // reward byte by outcome code 0..7 (two state words)
@@ -551,7 +563,10 @@ struct RockEnv {
     static constexpr uint32_t REC_ROCK = 1u << 31;           // second word of a one-state-word entry: a rock lies under this SAMPLE
     static constexpr uint32_t TIE_SPAN = 32u;                // H - E below this: the high word may leave the draw undecided
     // first word of a one-state-word CHECK entry from the threshold's high part T = thr >> 26 <= 2^27
-    static __device__ __forceinline__ uint32_t rec_thr_word(uint32_t T) { return T >= (1u << 27) ? 0xFFFFFFFFu : T << 5; }
+    // (INS: the saturated word keeps its low five bits clear — they are the insert's width, 0 for a CHECK — and every H from
+    // 0xFFFFFFE0 up passes the filter instead: rec_sensor_exact finds (H >> 5) < 2^27 = T, correct, as it must be)
+    template <bool INS = false>
+    static __device__ __forceinline__ uint32_t rec_thr_word(uint32_t T) { return T >= (1u << 27) ? (INS ? 0xFFFFFFE0u : 0xFFFFFFFFu) : T << 5; }
     // second word of a one-state-word entry: step `c` (-1, 0, +1) at bit offset `off`, ob mask, the record's reward byte and done bit
     static __device__ __forceinline__ uint32_t rec_f(uint32_t off, int c, uint32_t ob_mask, uint32_t oc)
     {
@@ -563,34 +578,50 @@ struct RockEnv {
     // offsets: a move's 24 (x) or 28 (y), a rock's 2 j.  No step carries out of its field in either layout: a move that stays
     // inside keeps its nibble (and y is the word's top nibble), and a SAMPLE takes a code of 0 or 2 to 1 — + 1 on 0, - 1 on 2,
     // neither leaves the two bits — so the last rock of a 12-rock board, at bits 22-23 right under x, never reaches the position.
+    // INS (with ROT, K <= RESET_NUMERIC_K: steps_quad_kernel): the state changes by ONE MASKED INSERT.  Every change a step makes
+    // writes a value the (action, position) entry already knows into a field it already knows — a move that stays inside the
+    // nibble x +- 1 or y +- 1, a SAMPLE on a rock the code 1 (over a collected rock's 1 as well, so the state half does not ask
+    // whether the rock was live), everything else nothing — so the entry's first word, which only a CHECK's compare reads,
+    // holds for every other action the field's width in bits 0-4 and the value where the field lies:
+    //   a move inside: (new nibble << off) | 4;   SAMPLE on a rock with an id < K: (1 << off) | 2;   else 0 (width 0: no change);
+    //   CHECK: T << 5 as before (width 0), saturated to 0xFFFFFFE0 (rec_thr_word<true>).
+    // rec_finish: m = ((1 << E[4:0]) - 1) << f[4:0] (v_bfm_b32), s' = (E & m) | (s & ~m) (v_bfi_b32) — two instructions where
+    // the step form takes four (v_sub_u32, v_bfe_i32, v_cndmask_b32, v_lshl_add_u32); the second word's step field stays 0.
+    // The low five bits of the state word must then be clear of codes: rock j's code lies at bit INS_ROCK0 + 2 j = 5 + 2 j, the
+    // last of eight rocks ends at bit 20, bits 21-23 and 0-4 are zero, and the entry's address (rec_lookup) needs no mask.
+    // Against a non-CHECK entry the tie filter H - E < TIE_SPAN passes 32 values of H as before (2^-27 per lane-step), its
+    // outcome unused; the slot rec_sensor_exact derives from such an entry's offset is 9 (off 24), 11 (28) or 13 (0): below 16.
     static constexpr uint32_t ROT_POS = 24u;
-    template <bool ROT = false>
+    template <bool ROT = false, bool INS = false>
     static __device__ __forceinline__ void build_rec_tab(RecTab &tab, const Shared &sh, const Params &p, int pos)
     {
         static_assert(!ROT || W == 1, "the rotated layout is the one-state-word loops'");
-        constexpr uint32_t POS0 = ROT ? ROT_POS : 0u, ROCK0 = ROT ? 0u : 8u;     // bit offsets of x and of rock 0's code
+        static_assert(!INS || ROT, "the insert layout is a rotated one");
+        constexpr uint32_t POS0 = ROT ? ROT_POS : 0u, ROCK0 = INS ? INS_ROCK0 : ROT ? 0u : 8u;     // bit offsets of x and of rock 0's code
         const uint32_t x = (uint32_t)pos & 15u, y = (uint32_t)pos >> 4, size = (uint32_t)p.size, K = (uint32_t)p.num_rocks;
         const int id = sh.grid[x * 16 + y];
         const uint32_t NOTHING = 6u << 28, PENALTY = (STOCH ? 6u : 1u) << 28, EXIT_EAST = 3u << 28;
         const uint32_t NO_TIE = 1u << 27;                                        // (two state words)
         for (int a = 0; a < 5 + (int)K && a < TAB_ACTIONS; ++a) {
-            uint32_t e, f;
+            uint32_t e, f, ins = 0u;                                             // ins: an INS entry's first word (not a CHECK's)
             if (a < 4) {
                 const uint32_t nx = x + (uint32_t)((a == 1) - (a == 3)), ny = y + (uint32_t)((a == 0) - (a == 2));
                 const bool inside = max(nx, ny) < size;
                 e = inside ? (((uint32_t)pos ^ (nx | (ny << 4))) | NOTHING) : (a == 1 ? EXIT_EAST : PENALTY);
                 e |= NO_TIE;
                 // x +- 1 is the state word +- 1, y +- 1 is +- 1 << 4 (no carry leaves the nibble of a move that stays inside)
-                f = rec_f(POS0 + ((a & 1) ? 0u : 4u), inside ? (a < 2 ? 1 : -1) : 0, 0u, e >> 28 & 7u);
+                f = rec_f(POS0 + ((a & 1) ? 0u : 4u), inside && !INS ? (a < 2 ? 1 : -1) : 0, 0u, e >> 28 & 7u);
+                if (inside) ins = (((a & 1) ? nx : ny) << (f & 31u)) | 4u;
             } else if (a == 4) {
                 const bool rock = (uint32_t)id < K;
                 e = (rock ? ((8u + 2u * (uint32_t)id) | 0x80000000u) : 0u) | PENALTY | NO_TIE;
                 f = rec_f(rock ? ROCK0 + 2u * (uint32_t)id : 0u, 0, 0u, e >> 28 & 7u);
+                if (rock) ins = (1u << (f & 31u)) | 2u;
             } else {
                 e = sh.thr[__builtin_amdgcn_sad_u8(x | (y << 8), sh.rpos[a - 5], 0u) & 31u].x | NOTHING;
                 f = rec_f(ROCK0 + 2u * (uint32_t)(a - 5), 0, 3u, 6u);
             }
-            if constexpr (W == 1) tab.e[a][pos] = make_uint2(a > 4 ? rec_thr_word(e & ~NOTHING) : 0xFFFFFFFFu, f | (a == 4 ? e & REC_ROCK : 0u));
+            if constexpr (W == 1) tab.e[a][pos] = make_uint2(a > 4 ? rec_thr_word<INS>(e & ~NOTHING) : INS ? ins : 0xFFFFFFFFu, f | (a == 4 ? e & REC_ROCK : 0u));
             else tab.e[a][pos] = e;
         }
     }
@@ -601,14 +632,14 @@ struct RockEnv {
     // The one-state-word lane step in its two halves, for the loops that issue the table reads of all of a thread's lanes before
     // they use the first (steps_quad_kernel): rec_lookup reads the entry, the raw sensor word compares with its first word
     // (`correct` = H < e; H - e < TIE_SPAN: rec_sensor_exact decides instead), rec_finish makes the record and the new state.
-    // ROT: the state word is kept rotated (build_rec_tab<true>).
-    template <bool ROT = false>
+    // ROT: the state word is kept rotated (build_rec_tab<true>); INS: ... in the insert layout (build_rec_tab<true, true>).
+    template <bool ROT = false, bool INS = false>
     static __device__ __forceinline__ uint2 rec_lookup(const RecTab &tab, uint32_t s, uint32_t a)
     {
         if constexpr (ROT) {
             // the entry's byte offset a << 11 | position << 3 in one v_alignbit_b32 (the position byte is the word's top) and one
-            // v_and_b32 that clears the three code bits that came along
-            const uint32_t off = __builtin_amdgcn_alignbit(a, s, ROT_POS - 3u) & ~7u;
+            // v_and_b32 that clears the three code bits that came along (INS: bits 21-23 of the word are zero, nothing to clear)
+            const uint32_t off = __builtin_amdgcn_alignbit(a, s, ROT_POS - 3u) & (INS ? ~0u : ~7u);
             return *reinterpret_cast<const uint2 *>(reinterpret_cast<const char *>(&tab.e[0][0]) + off);
         } else return tab.e[a][s & 0xFFu];
     }
@@ -617,10 +648,10 @@ struct RockEnv {
     // offset, not the action, so that a tape-driven loop's rare path does not keep a tape row it wants to load over alive.  The
     // filter also passes H = 0xFFFFFFFF and H < 31 on a move or a SAMPLE: their offsets name some rock slot below 16, every
     // read stays inside its table, and rec_finish does not use `correct` for them.
-    template <bool ROT = false, class LowWord>
+    template <bool ROT = false, bool INS = false, class LowWord>
     static __device__ __forceinline__ bool rec_sensor_exact(const Shared &sh, uint32_t s, uint32_t f, uint32_t H, LowWord lo)
     {
-        const uint32_t pos = ROT ? s >> ROT_POS : s, r = (((f & 31u) - (ROT ? 0u : 8u)) >> 1) & 15u;
+        const uint32_t pos = ROT ? s >> ROT_POS : s, r = (((f & 31u) - (INS ? INS_ROCK0 : ROT ? 0u : 8u)) >> 1) & 15u;
         const uint2 t = sh.thr[__builtin_amdgcn_sad_u8((pos & 15u) | ((pos & 0xF0u) << 4), sh.rpos[r], 0u) & 31u];
         // (the low word is drawn whatever the comparison says — all but 2^-5 of the lanes that come here need it — and pinned
         // before the comparison, so that the rare path is one straight block)
@@ -629,6 +660,7 @@ struct RockEnv {
         asm volatile("" : "+v"(kl));
         return kh == t.x ? kl <= t.y : kh < t.x;
     }
+    template <bool INS = false>
     static __device__ __forceinline__ void rec_finish(const uint2 ef, uint32_t &s, uint32_t a, bool correct, uint32_t fresh, uint32_t &rec)
     {
         const uint32_t f = ef.y;
@@ -643,9 +675,24 @@ struct RockEnv {
         // a sampled rock's code IS its outcome: 0 -> -10 (0xF6), 2 -> +10 (0x0A), never done; the action byte is SAMPLE's
         const uint32_t rok = 0x00F60004u - q * 0x00760000u;
         rec = ok ? rok : rfb;
-        // the state moves by a step of -1, 0 or +1 at the entry's offset: a move's nibble, or a sampled rock's code -> 1
-        const int c = ok ? 1 - (int)q : __builtin_amdgcn_sbfe((int)f, 5u, 2u);
-        const uint32_t moved = s + ((uint32_t)c << (f & 31u));
+        uint32_t moved;
+        if constexpr (INS) {
+            // the entry's first word is inserted at the entry's offset, as wide as its low five bits say (a move's nibble, a
+            // sampled rock's code -> 1, width 0: nothing): v_bfm_b32 reads bits 0-4 of both operands itself, v_bfi_b32 follows
+            // (hipcc forms neither from the C expressions: three shifts and a v_not_b32 for the mask, two v_and_b32, a v_not_b32
+            // and a v_or_b32 for the insert)
+            uint32_t m;
+            asm("v_bfm_b32 %0, %1, %2" : "=v"(m) : "v"(ef.x), "v"(f));
+            asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(moved) : "v"(m), "v"(ef.x), "v"(s));
+            // (the record passes through a register of its own: with the state half gone from the lanes' common subexpressions
+            // the compiler otherwise builds the four records of a thread's 16-byte store as two-element vectors and splits
+            // their v_and_or_b32 back into a v_and_b32 and a v_or_b32 each — four instructions more per thread-step)
+            asm("" : "+v"(rec));
+        } else {
+            // the state moves by a step of -1, 0 or +1 at the entry's offset: a move's nibble, or a sampled rock's code -> 1
+            const int c = ok ? 1 - (int)q : __builtin_amdgcn_sbfe((int)f, 5u, 2u);
+            moved = s + ((uint32_t)c << (f & 31u));
+        }
         s = rec >= (1u << 24) ? fresh : moved;                              // done: byte 3 of the finished record
     }
     template <class LowWord>

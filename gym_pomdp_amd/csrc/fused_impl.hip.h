@@ -362,6 +362,8 @@ __global__ __launch_bounds__(BLOCK) void steps_kernel(uint32_t *__restrict__ sta
 // compare, ONE exec-masked branch for the lanes whose sensor draw the high word leaves undecided (with the reset-tie filter:
 // two per step, where each lane had its own read -> wait -> compare -> branch), then the records — on a state word kept
 // rotated in registers (rock.hip.h: RecTab), and packed records leave through a scalar row base (traj_out.hip.h: PackedRowOut).
+// With at most eight rocks (round 15, INS) the rotated word carries the codes five bits up and a step changes it by one masked
+// insert of the table entry's first word (v_bfm_b32, v_bfi_b32): 154 vector instructions per thread-step in the packed loop, not 162.
 // LPT = 2 (round 6): HALF a quad per thread, for the shards that leave the quad loop two waves per SIMD or fewer (2^19 lanes
 // — half of a 2^20-lane batch — ran the pooled two-lanes-per-thread steps_kernel at 0.46 of its issue floor).  The quad's
 // STEP block (and StochasticRock's gate block) is time-shared by the quad's two threads exactly like the policy's block
@@ -382,10 +384,13 @@ __device__ __forceinline__ void steps_quad_body(uint32_t *__restrict__ state, in
     // one state word: the loop keeps it rotated right by 8 — rock codes from bit 0, the position byte on top — so that a fresh
     // episode is one v_and_or_b32 of the lane's sensor word (RockEnv::build_rec_tab<true>); memory keeps its layout
     constexpr bool ROT = W == 1;
+    // ... and, with the numeric filter's boards (at most RockEnv::RESET_NUMERIC_K rocks), the codes five bits up, clear of the
+    // word's low bits: the state changes by one masked insert of the table entry's first word (RockEnv::build_rec_tab<true, true>)
+    constexpr bool INS = ROT && NUMERIC;
     using S = typename Env::S;
     __shared__ typename Env::Shared sh;
     // the lane step yields the lane's packed record straight from RecTab (one state word: RockEnv::rec_lookup / rec_finish, 17
-    // vector instructions per lane-step and one for the fresh episode it may need; two: RockEnv::step_rec)
+    // vector instructions per lane-step and one for the fresh episode it may need — INS: 15 and two; two words: RockEnv::step_rec)
     __shared__ typename Env::RecTab tab;
     const uint32_t n_act = (uint32_t)Env::n_actions(p);
     // a quad per thread on a tape: the loop unrolled by two, the tape read two steps ahead (TapeQuadAhead)
@@ -415,13 +420,14 @@ __device__ __forceinline__ void steps_quad_body(uint32_t *__restrict__ state, in
         cx.first(gen_first, a_cur);
 #pragma unroll
         for (int j = 0; j < LPT; ++j) {
-            if constexpr (ROT) st[j].s = __builtin_amdgcn_alignbit(s_lo[j], s_lo[j], 8u);
+            if constexpr (INS) st[j].s = (s_lo[j] << Env::ROT_POS) | ((s_lo[j] >> (8u - Env::INS_ROCK0)) & (0xFFFFu << Env::INS_ROCK0));
+            else if constexpr (ROT) st[j].s = __builtin_amdgcn_alignbit(s_lo[j], s_lo[j], 8u);
             else st[j].s = (S)((uint64_t)s_lo[j] | ((uint64_t)s_hi[j] << 32));
         }
     }
     Env::stage(sh, p, (int)threadIdx.x);
     __syncthreads();
-    Env::template build_rec_tab<ROT>(tab, sh, p, (int)threadIdx.x);
+    Env::template build_rec_tab<ROT, INS>(tab, sh, p, (int)threadIdx.x);
     __syncthreads();
     const int K = p.num_rocks;
     const uint32_t start = (uint32_t)p.start_x | ((uint32_t)p.start_y << 4);
@@ -484,9 +490,9 @@ __device__ __forceinline__ void steps_quad_body(uint32_t *__restrict__ state, in
             // compare and the records
             uint32_t fresh[LPT], sn[LPT];
             uint2 ef[LPT];
-            Env::template fresh_states<LPT, true, NUMERIC>(H, key, glane0, K, start_rot, tie_bound, fresh);
+            Env::template fresh_states<LPT, true, NUMERIC, INS>(H, key, glane0, K, start_rot, tie_bound, fresh);
 #pragma unroll
-            for (int j = 0; j < LPT; ++j) ef[j] = Env::template rec_lookup<true>(tab, st[j].s, valid[j] ? a_taken[j] : 0u);
+            for (int j = 0; j < LPT; ++j) ef[j] = Env::template rec_lookup<true, INS>(tab, st[j].s, valid[j] ? a_taken[j] : 0u);
             {   // all of them have landed: one wait (each entry passes as the register pair its read filled: no copies)
                 uint64_t w[LPT];
 #pragma unroll
@@ -508,12 +514,12 @@ __device__ __forceinline__ void steps_quad_body(uint32_t *__restrict__ state, in
 #pragma unroll
                 for (int j = 0; j < LPT; ++j)
                     if (near[j] < Env::TIE_SPAN)
-                        correct[j] = Env::template rec_sensor_exact<true>(sh, st[j].s, ef[j].y, H[j], [&]() { return low_word(j); });
+                        correct[j] = Env::template rec_sensor_exact<true, INS>(sh, st[j].s, ef[j].y, H[j], [&]() { return low_word(j); });
             }
 #pragma unroll
             for (int j = 0; j < LPT; ++j) {
                 sn[j] = st[j].s;
-                Env::rec_finish(ef[j], sn[j], valid[j] ? a_taken[j] : 0u, correct[j], fresh[j], rec[j]);
+                Env::template rec_finish<INS>(ef[j], sn[j], valid[j] ? a_taken[j] : 0u, correct[j], fresh[j], rec[j]);
             }
 #pragma unroll
             for (int j = 0; j < LPT; ++j) {
@@ -573,7 +579,11 @@ __device__ __forceinline__ void steps_quad_body(uint32_t *__restrict__ state, in
     cx.finish(k_steps);
     uint32_t w_lo[LPT];
 #pragma unroll
-    for (int j = 0; j < LPT; ++j) w_lo[j] = ROT ? __builtin_amdgcn_alignbit((uint32_t)st[j].s, (uint32_t)st[j].s, 24u) : (uint32_t)st[j].s;
+    for (int j = 0; j < LPT; ++j) {
+        const uint32_t sj = (uint32_t)st[j].s;
+        w_lo[j] = INS ? (sj >> Env::ROT_POS) | ((sj & (0xFFFFu << Env::INS_ROCK0)) << (8u - Env::INS_ROCK0))
+                      : ROT ? __builtin_amdgcn_alignbit(sj, sj, 24u) : sj;
+    }
     if constexpr (LPT == 4) {
         st_stream4(state + l0, w_lo[0], w_lo[1], w_lo[2], w_lo[3]);
         if (W == 2)

@@ -62,6 +62,9 @@ def make_params(board_size=7, num_rocks=8, stochastic=False, p_move=.8):
     for d in range(32):
         p.thr[d] = tables.ROCK_THR[min(d, len(tables.ROCK_THR) - 1)]
         p.eff[d] = tables.ROCK_EFF[min(d, len(tables.ROCK_EFF) - 1)]
+        # the sensor is never worse than a coin: thr >> 26 >= 2^26 (the quad loop's table reads a CHECK entry's low five bits,
+        # (thr >> 26) << 5, as a width of zero and needs thr >> 26 >= 1: rock.hip.h, build_rec_tab)
+        assert 1 << 52 <= p.thr[d] <= 1 << 53, (d, p.thr[d])
     if stochastic:
         p.stochastic = 1
         if p_move == .8:

@@ -32,7 +32,7 @@ DEFAULT = ["steps_quad_kernel<pomdp::RockEnv<1, false>, ", "steps_quad_popc_kern
 # mnemonic -> the measured class that prices it (tools/valu_microbench.hip op names); anything else: DEFAULT_COST
 ALIAS = {
     "v_add_u32": "v_add_u32", "v_sub_u32": "v_sub_u32", "v_subrev_u32": "v_sub_u32", "v_add_i32": "v_add_u32",
-    "v_and_b32": "v_and_b32", "v_or_b32": "v_or_b32", "v_xor_b32": "v_xor_b32", "v_not_b32": "v_mov_b32", "v_bfi_b32": "v_and_or_b32",
+    "v_and_b32": "v_and_b32", "v_or_b32": "v_or_b32", "v_xor_b32": "v_xor_b32", "v_not_b32": "v_mov_b32", "v_bfi_b32": "v_bfi_b32", "v_bfm_b32": "v_bfm_b32",
     "v_bitop3_b32": "v_bitop3_b32", "v_cndmask_b32": "v_cndmask_b32",
     "v_lshrrev_b32": "v_lshrrev_b32", "v_lshlrev_b32": "v_lshrrev_b32", "v_ashrrev_i32": "v_lshrrev_b32",
     "v_lshl_or_b32": "v_lshl_or_b32", "v_and_or_b32": "v_and_or_b32", "v_or3_b32": "v_or3_b32", "v_add3_u32": "v_add3_u32",

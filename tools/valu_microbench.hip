@@ -23,12 +23,12 @@ constexpr int R = 2048;    // loop iterations
 
 // one instruction per accumulator per iteration; the template parameter picks the class
 enum Op { ADD, AND, XOR, BITOP3, CNDMASK, LSHR, LSHL_OR, AND_OR, MUL_HI, MUL_LO, MAD_U64, SAD_U8, BFE, CMP, MOV, DPP_MOV, BCNT, ROTR, MIN_U32,
-          ADD3, PERM, MAD_U32_U24, LSHL_B64, ADD_CO, ADD_F64, MUL_F64, CVT_F64_I32, OR3, LSHL_ADD, XAD, SUB, OR, FFBL, N_OPS };
+          ADD3, PERM, MAD_U32_U24, LSHL_B64, ADD_CO, ADD_F64, MUL_F64, CVT_F64_I32, OR3, LSHL_ADD, XAD, SUB, OR, FFBL, BFM, BFI, N_OPS };
 static const char *OP_NAME[N_OPS] = {"v_add_u32", "v_and_b32", "v_xor_b32", "v_bitop3_b32", "v_cndmask_b32", "v_lshrrev_b32", "v_lshl_or_b32",
                                      "v_and_or_b32", "v_mul_hi_u32", "v_mul_lo_u32", "v_mad_u64_u32", "v_sad_u8", "v_bfe_u32", "v_cmp_lt_u32",
                                      "v_mov_b32", "v_mov_b32_dpp", "v_bcnt_u32_b32", "v_alignbit_b32", "v_min_u32", "v_add3_u32", "v_perm_b32",
                                      "v_mad_u32_u24", "v_lshlrev_b64", "v_add_co_u32", "v_add_f64", "v_mul_f64", "v_cvt_f64_i32", "v_or3_b32",
-                                     "v_lshl_add_u32", "v_xad_u32", "v_sub_u32", "v_or_b32", "v_ffbl_b32"};
+                                     "v_lshl_add_u32", "v_xad_u32", "v_sub_u32", "v_or_b32", "v_ffbl_b32", "v_bfm_b32", "v_bfi_b32"};
 
 template <int OP>
 __global__ __launch_bounds__(1024) void bench(uint32_t *out, uint64_t *cycles, uint32_t seed)
@@ -76,6 +76,8 @@ __global__ __launch_bounds__(1024) void bench(uint32_t *out, uint64_t *cycles, u
             if (OP == SUB) asm volatile("v_sub_u32 %0, %0, %1" : "+v"(x[i]) : "v"(c));
             if (OP == OR) asm volatile("v_or_b32 %0, %1, %0" : "+v"(x[i]) : "v"(c));
             if (OP == FFBL) asm volatile("v_ffbl_b32 %0, %0" : "+v"(x[i]));
+            if (OP == BFM) asm volatile("v_bfm_b32 %0, %0, %1" : "+v"(x[i]) : "v"(c));
+            if (OP == BFI) asm volatile("v_bfi_b32 %0, %1, %2, %0" : "+v"(x[i]) : "v"(c), "s"(seed));
         }
     }
     const uint64_t t1 = __builtin_readcyclecounter(), r1 = wall_clock64();
