@@ -210,8 +210,8 @@ struct RockEnv {
     // per launch, for K <= RESET_NUMERIC_K): the filter is the smallest of the thread's words against `bound` (2^-11 per lane
     // at K = 8) and no bit is counted off the branch.  Above, the bound passes too many lanes (one in 32 at K = 11) and the
     // filter is the popcount test itself.
-    // INS (with ROT, K <= RESET_NUMERIC_K): the layout of build_rec_tab<true, true>, rock 0's code at bit INS_ROCK0 — the word
-    // shifted up by that, then the same v_and_or_b32.
+    // INS (with ROT, K <= RESET_NUMERIC_K): the layout of build_rec_tab_wide, rock 0's code at bit INS_ROCK0 — the word
+    // shifted up by that, then the same v_and_or_b32 (`start`: wide_start).
     static constexpr int RESET_NUMERIC_K = 8;
     static constexpr uint32_t INS_ROCK0 = 5u;
     static __device__ __forceinline__ uint32_t reset_tie_bound(int K) { return 1u << (2 * min(K, RESET_NUMERIC_K) + 5); }
@@ -551,10 +551,11 @@ struct RockEnv {
     // fresh episode one v_and_or_b32 of the lane's sensor word — its rocks' codes are where the word has them — instead of a
     // v_and_b32 and a v_lshl_or_b32: 17 + 1 vector instructions per lane-step there and three per thread for the filter
     // (v_min_u32, v_min3_u32, one compare).  The table differs in its bit offsets only (build_rec_tab<true>).
-    // With at most RESET_NUMERIC_K = 8 rocks (INS, steps_quad_kernel; build_rec_tab<true, true> below) the codes sit five bits
-    // higher and the state half of the step is one masked insert of the entry's first word: the v_sub_u32, v_bfe_i32,
-    // v_cndmask_b32 and v_lshl_add_u32 of the step form become a v_bfm_b32 and a v_bfi_b32, the address loses its v_and_b32 and
-    // the fresh episode gains a v_lshlrev_b32 — 15 + 1 per lane-step.  steps_quad_popc_kernel (9 to 12 rocks) keeps 17 + 1.
+    // With at most RESET_NUMERIC_K = 8 rocks (INS, steps_quad_kernel) the entry is 16 bytes (RecTabWide, build_rec_tab_wide
+    // below) and holds the insert mask and both finished records ready-made: the state half of the step is one v_bfi_b32, the
+    // record one v_cndmask_b32 between two words of the entry — 12 vector instructions per lane-step (v_alignbit_b32,
+    // v_sub_co_u32, v_bfe_u32, three compares of q and the flag, v_cndmask_b32, v_mad_i32_i24, v_cndmask_b32, v_bfi_b32, the
+    // done compare, v_cndmask_b32) and 2 for the fresh episode.  steps_quad_popc_kernel (9 to 12 rocks) keeps 17 + 1.
     // Two state words keep 4-byte entries (21 x 256 x 8 = 42 KB would leave three workgroups per CU), test the action, and
     // look the reward byte up by outcome code with one v_perm_b32 in an 8-byte constant; that branch is as it was.
     static constexpr uint32_t REC_LUT_LO = 0x0A0A9CF6u, REC_LUT_HI = 0x00000000u;   // reward byte by outcome code 0..7 (two state words)
@@ -563,8 +564,9 @@ struct RockEnv {
     static constexpr uint32_t REC_ROCK = 1u << 31;           // second word of a one-state-word entry: a rock lies under this SAMPLE
     static constexpr uint32_t TIE_SPAN = 32u;                // H - E below this: the high word may leave the draw undecided
     // first word of a one-state-word CHECK entry from the threshold's high part T = thr >> 26 <= 2^27
-    // (INS: the saturated word keeps its low five bits clear — they are the insert's width, 0 for a CHECK — and every H from
-    // 0xFFFFFFE0 up passes the filter instead: rec_sensor_exact finds (H >> 5) < 2^27 = T, correct, as it must be)
+    // (INS: the saturated word keeps its low five bits clear — a wide entry's mask word has the rock's bit offset there, and no
+    // state bit may come from under it — and every H from 0xFFFFFFE0 up passes the filter instead: rec_sensor_exact_wide finds
+    // (H >> 5) < 2^27 = T, correct, as it must be)
     template <bool INS = false>
     static __device__ __forceinline__ uint32_t rec_thr_word(uint32_t T) { return T >= (1u << 27) ? (INS ? 0xFFFFFFE0u : 0xFFFFFFFFu) : T << 5; }
     // second word of a one-state-word entry: step `c` (-1, 0, +1) at bit offset `off`, ob mask, the record's reward byte and done bit
@@ -578,50 +580,34 @@ struct RockEnv {
     // offsets: a move's 24 (x) or 28 (y), a rock's 2 j.  No step carries out of its field in either layout: a move that stays
     // inside keeps its nibble (and y is the word's top nibble), and a SAMPLE takes a code of 0 or 2 to 1 — + 1 on 0, - 1 on 2,
     // neither leaves the two bits — so the last rock of a 12-rock board, at bits 22-23 right under x, never reaches the position.
-    // INS (with ROT, K <= RESET_NUMERIC_K: steps_quad_kernel): the state changes by ONE MASKED INSERT.  Every change a step makes
-    // writes a value the (action, position) entry already knows into a field it already knows — a move that stays inside the
-    // nibble x +- 1 or y +- 1, a SAMPLE on a rock the code 1 (over a collected rock's 1 as well, so the state half does not ask
-    // whether the rock was live), everything else nothing — so the entry's first word, which only a CHECK's compare reads,
-    // holds for every other action the field's width in bits 0-4 and the value where the field lies:
-    //   a move inside: (new nibble << off) | 4;   SAMPLE on a rock with an id < K: (1 << off) | 2;   else 0 (width 0: no change);
-    //   CHECK: T << 5 as before (width 0), saturated to 0xFFFFFFE0 (rec_thr_word<true>).
-    // rec_finish: m = ((1 << E[4:0]) - 1) << f[4:0] (v_bfm_b32), s' = (E & m) | (s & ~m) (v_bfi_b32) — two instructions where
-    // the step form takes four (v_sub_u32, v_bfe_i32, v_cndmask_b32, v_lshl_add_u32); the second word's step field stays 0.
-    // The low five bits of the state word must then be clear of codes: rock j's code lies at bit INS_ROCK0 + 2 j = 5 + 2 j, the
-    // last of eight rocks ends at bit 20, bits 21-23 and 0-4 are zero, and the entry's address (rec_lookup) needs no mask.
-    // Against a non-CHECK entry the tie filter H - E < TIE_SPAN passes 32 values of H as before (2^-27 per lane-step), its
-    // outcome unused; the slot rec_sensor_exact derives from such an entry's offset is 9 (off 24), 11 (28) or 13 (0): below 16.
     static constexpr uint32_t ROT_POS = 24u;
-    template <bool ROT = false, bool INS = false>
+    template <bool ROT = false>
     static __device__ __forceinline__ void build_rec_tab(RecTab &tab, const Shared &sh, const Params &p, int pos)
     {
         static_assert(!ROT || W == 1, "the rotated layout is the one-state-word loops'");
-        static_assert(!INS || ROT, "the insert layout is a rotated one");
-        constexpr uint32_t POS0 = ROT ? ROT_POS : 0u, ROCK0 = INS ? INS_ROCK0 : ROT ? 0u : 8u;     // bit offsets of x and of rock 0's code
+        constexpr uint32_t POS0 = ROT ? ROT_POS : 0u, ROCK0 = ROT ? 0u : 8u;     // bit offsets of x and of rock 0's code
         const uint32_t x = (uint32_t)pos & 15u, y = (uint32_t)pos >> 4, size = (uint32_t)p.size, K = (uint32_t)p.num_rocks;
         const int id = sh.grid[x * 16 + y];
         const uint32_t NOTHING = 6u << 28, PENALTY = (STOCH ? 6u : 1u) << 28, EXIT_EAST = 3u << 28;
         const uint32_t NO_TIE = 1u << 27;                                        // (two state words)
         for (int a = 0; a < 5 + (int)K && a < TAB_ACTIONS; ++a) {
-            uint32_t e, f, ins = 0u;                                             // ins: an INS entry's first word (not a CHECK's)
+            uint32_t e, f;
             if (a < 4) {
                 const uint32_t nx = x + (uint32_t)((a == 1) - (a == 3)), ny = y + (uint32_t)((a == 0) - (a == 2));
                 const bool inside = max(nx, ny) < size;
                 e = inside ? (((uint32_t)pos ^ (nx | (ny << 4))) | NOTHING) : (a == 1 ? EXIT_EAST : PENALTY);
                 e |= NO_TIE;
                 // x +- 1 is the state word +- 1, y +- 1 is +- 1 << 4 (no carry leaves the nibble of a move that stays inside)
-                f = rec_f(POS0 + ((a & 1) ? 0u : 4u), inside && !INS ? (a < 2 ? 1 : -1) : 0, 0u, e >> 28 & 7u);
-                if (inside) ins = (((a & 1) ? nx : ny) << (f & 31u)) | 4u;
+                f = rec_f(POS0 + ((a & 1) ? 0u : 4u), inside ? (a < 2 ? 1 : -1) : 0, 0u, e >> 28 & 7u);
             } else if (a == 4) {
                 const bool rock = (uint32_t)id < K;
                 e = (rock ? ((8u + 2u * (uint32_t)id) | 0x80000000u) : 0u) | PENALTY | NO_TIE;
                 f = rec_f(rock ? ROCK0 + 2u * (uint32_t)id : 0u, 0, 0u, e >> 28 & 7u);
-                if (rock) ins = (1u << (f & 31u)) | 2u;
             } else {
                 e = sh.thr[__builtin_amdgcn_sad_u8(x | (y << 8), sh.rpos[a - 5], 0u) & 31u].x | NOTHING;
                 f = rec_f(ROCK0 + 2u * (uint32_t)(a - 5), 0, 3u, 6u);
             }
-            if constexpr (W == 1) tab.e[a][pos] = make_uint2(a > 4 ? rec_thr_word<INS>(e & ~NOTHING) : INS ? ins : 0xFFFFFFFFu, f | (a == 4 ? e & REC_ROCK : 0u));
+            if constexpr (W == 1) tab.e[a][pos] = make_uint2(a > 4 ? rec_thr_word(e & ~NOTHING) : 0xFFFFFFFFu, f | (a == 4 ? e & REC_ROCK : 0u));
             else tab.e[a][pos] = e;
         }
     }
@@ -632,14 +618,14 @@ struct RockEnv {
     // The one-state-word lane step in its two halves, for the loops that issue the table reads of all of a thread's lanes before
     // they use the first (steps_quad_kernel): rec_lookup reads the entry, the raw sensor word compares with its first word
     // (`correct` = H < e; H - e < TIE_SPAN: rec_sensor_exact decides instead), rec_finish makes the record and the new state.
-    // ROT: the state word is kept rotated (build_rec_tab<true>); INS: ... in the insert layout (build_rec_tab<true, true>).
-    template <bool ROT = false, bool INS = false>
+    // ROT: the state word is kept rotated (build_rec_tab<true>).
+    template <bool ROT = false>
     static __device__ __forceinline__ uint2 rec_lookup(const RecTab &tab, uint32_t s, uint32_t a)
     {
         if constexpr (ROT) {
             // the entry's byte offset a << 11 | position << 3 in one v_alignbit_b32 (the position byte is the word's top) and one
-            // v_and_b32 that clears the three code bits that came along (INS: bits 21-23 of the word are zero, nothing to clear)
-            const uint32_t off = __builtin_amdgcn_alignbit(a, s, ROT_POS - 3u) & (INS ? ~0u : ~7u);
+            // v_and_b32 that clears the three code bits that came along
+            const uint32_t off = __builtin_amdgcn_alignbit(a, s, ROT_POS - 3u) & ~7u;
             return *reinterpret_cast<const uint2 *>(reinterpret_cast<const char *>(&tab.e[0][0]) + off);
         } else return tab.e[a][s & 0xFFu];
     }
@@ -648,11 +634,17 @@ struct RockEnv {
     // offset, not the action, so that a tape-driven loop's rare path does not keep a tape row it wants to load over alive.  The
     // filter also passes H = 0xFFFFFFFF and H < 31 on a move or a SAMPLE: their offsets name some rock slot below 16, every
     // read stays inside its table, and rec_finish does not use `correct` for them.
-    template <bool ROT = false, bool INS = false, class LowWord>
+    template <bool ROT = false, class LowWord>
     static __device__ __forceinline__ bool rec_sensor_exact(const Shared &sh, uint32_t s, uint32_t f, uint32_t H, LowWord lo)
     {
-        const uint32_t pos = ROT ? s >> ROT_POS : s, r = (((f & 31u) - (INS ? INS_ROCK0 : ROT ? 0u : 8u)) >> 1) & 15u;
-        const uint2 t = sh.thr[__builtin_amdgcn_sad_u8((pos & 15u) | ((pos & 0xF0u) << 4), sh.rpos[r], 0u) & 31u];
+        const uint32_t pos = ROT ? s >> ROT_POS : s, r = (((f & 31u) - (ROT ? 0u : 8u)) >> 1) & 15u;
+        return sensor_exact_at(sh, (pos & 15u) | ((pos & 0xF0u) << 4), r, H, lo);
+    }
+    // ... at the agent's bytes `xy` = x | y << 8, for rock slot r < 16
+    template <class LowWord>
+    static __device__ __forceinline__ bool sensor_exact_at(const Shared &sh, uint32_t xy, uint32_t r, uint32_t H, LowWord lo)
+    {
+        const uint2 t = sh.thr[__builtin_amdgcn_sad_u8(xy, sh.rpos[r], 0u) & 31u];
         // (the low word is drawn whatever the comparison says — all but 2^-5 of the lanes that come here need it — and pinned
         // before the comparison, so that the rare path is one straight block)
         const uint32_t kh = H >> 5;
@@ -660,7 +652,6 @@ struct RockEnv {
         asm volatile("" : "+v"(kl));
         return kh == t.x ? kl <= t.y : kh < t.x;
     }
-    template <bool INS = false>
     static __device__ __forceinline__ void rec_finish(const uint2 ef, uint32_t &s, uint32_t a, bool correct, uint32_t fresh, uint32_t &rec)
     {
         const uint32_t f = ef.y;
@@ -675,24 +666,106 @@ struct RockEnv {
         // a sampled rock's code IS its outcome: 0 -> -10 (0xF6), 2 -> +10 (0x0A), never done; the action byte is SAMPLE's
         const uint32_t rok = 0x00F60004u - q * 0x00760000u;
         rec = ok ? rok : rfb;
-        uint32_t moved;
-        if constexpr (INS) {
-            // the entry's first word is inserted at the entry's offset, as wide as its low five bits say (a move's nibble, a
-            // sampled rock's code -> 1, width 0: nothing): v_bfm_b32 reads bits 0-4 of both operands itself, v_bfi_b32 follows
-            // (hipcc forms neither from the C expressions: three shifts and a v_not_b32 for the mask, two v_and_b32, a v_not_b32
-            // and a v_or_b32 for the insert)
-            uint32_t m;
-            asm("v_bfm_b32 %0, %1, %2" : "=v"(m) : "v"(ef.x), "v"(f));
-            asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(moved) : "v"(m), "v"(ef.x), "v"(s));
-            // (the record passes through a register of its own: with the state half gone from the lanes' common subexpressions
-            // the compiler otherwise builds the four records of a thread's 16-byte store as two-element vectors and splits
-            // their v_and_or_b32 back into a v_and_b32 and a v_or_b32 each — four instructions more per thread-step)
-            asm("" : "+v"(rec));
-        } else {
-            // the state moves by a step of -1, 0 or +1 at the entry's offset: a move's nibble, or a sampled rock's code -> 1
-            const int c = ok ? 1 - (int)q : __builtin_amdgcn_sbfe((int)f, 5u, 2u);
-            moved = s + ((uint32_t)c << (f & 31u));
+        // the state moves by a step of -1, 0 or +1 at the entry's offset: a move's nibble, or a sampled rock's code -> 1
+        const int c = ok ? 1 - (int)q : __builtin_amdgcn_sbfe((int)f, 5u, 2u);
+        const uint32_t moved = s + ((uint32_t)c << (f & 31u));
+        s = rec >= (1u << 24) ? fresh : moved;                              // done: byte 3 of the finished record
+    }
+    // ---- 16-byte entries (INS: steps_quad_kernel, one state word, at most RESET_NUMERIC_K = 8 rocks) ---------------------------
+    // Every board with at most eight rocks has a side of at most 7 (RockSample(7,8), (7,7), (4,3), (2,1)): a coordinate is three
+    // bits, 13 actions x 128 slots x 16 bytes = 26 KB (less than RecTab's 34), and one ds_read_b128 brings {E, M, recA, recB}:
+    //   E    = what the raw sensor word compares with — a CHECK: T << 5, saturated to 0xFFFFFFE0 (rec_thr_word<true>) — else
+    //          the value a step writes, where it writes it: a move that stays inside the new coordinate in its field, a SAMPLE on
+    //          a rock with an id < K the code 1 (over a collected rock's 1 as well: the state half does not ask whether the rock
+    //          was live), everything else 0;
+    //   M    = the field E is inserted into — the moved coordinate's three bits, the sampled rock's two, else 0 (CHECKs too):
+    //          s' = (E & M) | (s & ~M), one v_bfi_b32 — plus, in bits 0-4, the bit offset of the rock the step is about (under
+    //          a SAMPLE, or the one a CHECK measures; 0 for a move), which v_bfe_u32 reads as it is, and in bit 31 (WIDE_ROCK)
+    //          "a rock with an id < K lies under this SAMPLE", one signed compare;
+    //   recA = the finished record (action byte, ob, reward byte, done bit) when no live rock is sampled and the reading matches
+    //          the rock (ob 2 on a CHECK), recB the same when it does not (ob 1); off a CHECK the two are equal.
+    // The state word in registers: bit 31 zero, y at bits 28-30, x at 25-27, rock j's code at bit INS_ROCK0 + 2 j = 5 + 2 j (the
+    // last of eight ends at bit 20), bits 21-24 and 0-4 zero.  The bits of M that are no field — 0-4 and 31 — lie over zeros of
+    // both s and E (E of a CHECK has M's fields empty, E of the others is a value inside a real field), so the insert keeps them
+    // zero; the entry's byte address a << 11 | y << 7 | x << 4 is one v_alignbit_b32(a, s, 21) with nothing to mask.  Memory
+    // keeps x | y << 4 | codes << 8 (wide_from_mem after the launch's load, wide_to_mem before its store; a coordinate above 7
+    // is no state of these boards: its fourth bit is dropped, every read stays inside the table).
+    // Against a non-CHECK entry the tie filter H - E < TIE_SPAN passes 32 values of H (2^-27 per lane-step), its outcome unused;
+    // the slot rec_sensor_exact_wide derives from a move's offset 0 is 13: below 16.
+    static constexpr int WIDE_ACTIONS = 5 + RESET_NUMERIC_K, WIDE_SLOTS = 128;
+    static constexpr int WIDE_SIDE = 7;                      // the launcher sends larger boards to steps_quad_popc_kernel
+    static constexpr uint32_t WIDE_X = 25u, WIDE_Y = 28u, WIDE_ROCK = 1u << 31;
+    struct RecTabWide { u32x4 e[WIDE_ACTIONS][WIDE_SLOTS]; };
+    static __device__ __forceinline__ uint32_t wide_from_mem(uint32_t m)
+    {
+        return ((m & 7u) << WIDE_X) | ((m & 0x70u) << (WIDE_Y - 4u)) | ((m >> (8u - INS_ROCK0)) & (0xFFFFu << INS_ROCK0));
+    }
+    static __device__ __forceinline__ uint32_t wide_to_mem(uint32_t s)
+    {
+        return ((s >> WIDE_X) & 7u) | ((s >> (WIDE_Y - 4u)) & 0x70u) | ((s & (0xFFFFu << INS_ROCK0)) << (8u - INS_ROCK0));
+    }
+    // the start cell (x | y << 4) where this layout has the position: what fresh_states<., true, true, true> ors in
+    static __device__ __forceinline__ uint32_t wide_start(uint32_t start) { return wide_from_mem(start & 0xFFu); }
+    // one thread per slot = x | y << 3, slot < WIDE_SLOTS (slots off the board are never read)
+    static __device__ __forceinline__ void build_rec_tab_wide(RecTabWide &tab, const Shared &sh, const Params &p, int slot)
+    {
+        static_assert(W == 1, "the wide entries are the one-state-word loops'");
+        const uint32_t x = (uint32_t)slot & 7u, y = ((uint32_t)slot >> 3) & 15u, size = (uint32_t)p.size, K = (uint32_t)p.num_rocks;
+        const int id = sh.grid[x * 16 + y];
+        const uint32_t penalty = STOCH ? 0u : (0x9Cu << 16) | (1u << 24);     // -100 and done (StochasticRock: nothing, rock.py:432, 503)
+        for (int a = 0; a < 5 + (int)K && a < WIDE_ACTIONS; ++a) {
+            uint32_t E = 0u, M = 0u, recA = (uint32_t)a, recB;
+            if (a < 4) {
+                const uint32_t nx = x + (uint32_t)((a == 1) - (a == 3)), ny = y + (uint32_t)((a == 0) - (a == 2));
+                const uint32_t off = (a & 1) ? WIDE_X : WIDE_Y;
+                if (max(nx, ny) < size) { E = ((a & 1) ? nx : ny) << off; M = 7u << off; }
+                else recA |= a == 1 ? (0x0Au << 16) | (1u << 24) : penalty;      // the east exit: +10 and done
+                recB = recA;
+            } else if (a == 4) {
+                const uint32_t off = INS_ROCK0 + 2u * (uint32_t)id;
+                if ((uint32_t)id < K) { E = 1u << off; M = (3u << off) | off | WIDE_ROCK; }
+                recA |= penalty;
+                recB = recA;
+            } else {
+                E = rec_thr_word<true>(sh.thr[__builtin_amdgcn_sad_u8(x | (y << 8), sh.rpos[a - 5], 0u) & 31u].x);
+                M = INS_ROCK0 + 2u * (uint32_t)(a - 5);
+                recB = recA | (1u << 8);
+                recA |= 2u << 8;
+            }
+            u32x4 e = {E, M, recA, recB};
+            tab.e[a][slot] = e;
         }
+    }
+    static __device__ __forceinline__ u32x4 rec_lookup_wide(const RecTabWide &tab, uint32_t s, uint32_t a)
+    {
+        const uint32_t off = __builtin_amdgcn_alignbit(a, s, WIDE_X - 4u);
+        return *reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(&tab.e[0][0]) + off);
+    }
+    // rec_sensor_exact for this layout: the position from the word's top, the rock slot from the mask word's offset
+    template <class LowWord>
+    static __device__ __forceinline__ bool rec_sensor_exact_wide(const Shared &sh, uint32_t s, uint32_t M, uint32_t H, LowWord lo)
+    {
+        const uint32_t r = (((M & 31u) - INS_ROCK0) >> 1) & 15u;
+        return sensor_exact_at(sh, ((s >> WIDE_X) & 7u) | (((s >> WIDE_Y) & 7u) << 8), r, H, lo);
+    }
+    static __device__ __forceinline__ void rec_finish_wide(const u32x4 e, uint32_t &s, bool correct, uint32_t fresh, uint32_t &rec)
+    {
+        const uint32_t M = e.y;
+        // the code of the rock this step is about, read at the mask word's offset (a move's 0: whatever this reads is not used)
+        const uint32_t q = __builtin_amdgcn_ubfe(s, M, 2u);
+        const bool ok = ((int32_t)M < 0) & (q != 1u);                       // SAMPLE: an uncollected rock with an id < K is underfoot
+        // the record when no live rock is sampled, ready-made: the reading gives the rock's state or it does not (CHECK rock
+        // a - 5, rock.py:171-175, 401-407: good = its code is 2)
+        const uint32_t rfb = ((q != 2u) != correct) ? e.z : e.w;
+        // a sampled rock's code IS its outcome: 0 -> -10 (0xF6), 2 -> +10 (0x0A), never done; the action byte is SAMPLE's
+        const uint32_t rok = 0x00F60004u - q * 0x00760000u;
+        rec = ok ? rok : rfb;
+        // (hipcc does not form v_bfi_b32 from the C expression: two v_and_b32, a v_not_b32 and a v_or_b32)
+        uint32_t moved;
+        asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(moved) : "v"(M), "v"(e.x), "v"(s));
+        // (the record passes through a register of its own: with the state half gone from the lanes' common subexpressions the
+        // compiler otherwise builds the four records of a thread's 16-byte store as two-element vectors)
+        asm("" : "+v"(rec));
         s = rec >= (1u << 24) ? fresh : moved;                              // done: byte 3 of the finished record
     }
     template <class LowWord>

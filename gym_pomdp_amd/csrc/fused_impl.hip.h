@@ -362,8 +362,9 @@ __global__ __launch_bounds__(BLOCK) void steps_kernel(uint32_t *__restrict__ sta
 // compare, ONE exec-masked branch for the lanes whose sensor draw the high word leaves undecided (with the reset-tie filter:
 // two per step, where each lane had its own read -> wait -> compare -> branch), then the records — on a state word kept
 // rotated in registers (rock.hip.h: RecTab), and packed records leave through a scalar row base (traj_out.hip.h: PackedRowOut).
-// With at most eight rocks (round 15, INS) the rotated word carries the codes five bits up and a step changes it by one masked
-// insert of the table entry's first word (v_bfm_b32, v_bfi_b32): 154 vector instructions per thread-step in the packed loop, not 162.
+// With at most eight rocks (round 15, INS) the word carries the codes five bits up and a step changes it by one masked insert
+// of the table entry's first word; since round 16 the entry is 16 bytes (rock.hip.h: RecTabWide, one ds_read_b128) and brings
+// the insert's mask and both finished records along: no v_bfm_b32, no v_and_or_b32 per lane.
 // LPT = 2 (round 6): HALF a quad per thread, for the shards that leave the quad loop two waves per SIMD or fewer (2^19 lanes
 // — half of a 2^20-lane batch — ran the pooled two-lanes-per-thread steps_kernel at 0.46 of its issue floor).  The quad's
 // STEP block (and StochasticRock's gate block) is time-shared by the quad's two threads exactly like the policy's block
@@ -384,14 +385,18 @@ __device__ __forceinline__ void steps_quad_body(uint32_t *__restrict__ state, in
     // one state word: the loop keeps it rotated right by 8 — rock codes from bit 0, the position byte on top — so that a fresh
     // episode is one v_and_or_b32 of the lane's sensor word (RockEnv::build_rec_tab<true>); memory keeps its layout
     constexpr bool ROT = W == 1;
-    // ... and, with the numeric filter's boards (at most RockEnv::RESET_NUMERIC_K rocks), the codes five bits up, clear of the
-    // word's low bits: the state changes by one masked insert of the table entry's first word (RockEnv::build_rec_tab<true, true>)
+    // ... and, with the numeric filter's boards (at most RockEnv::RESET_NUMERIC_K rocks, a side of at most 7), the codes five bits
+    // up, clear of the word's low bits, under two three-bit coordinates: the state changes by one masked insert from a 16-byte
+    // table entry (RockEnv::build_rec_tab_wide)
     constexpr bool INS = ROT && NUMERIC;
     using S = typename Env::S;
     __shared__ typename Env::Shared sh;
     // the lane step yields the lane's packed record straight from RecTab (one state word: RockEnv::rec_lookup / rec_finish, 17
-    // vector instructions per lane-step and one for the fresh episode it may need — INS: 15 and two; two words: RockEnv::step_rec)
-    __shared__ typename Env::RecTab tab;
+    // vector instructions per lane-step and one for the fresh episode it may need — INS: rec_lookup_wide / rec_finish_wide, 12
+    // and two; two words: RockEnv::step_rec)
+    using Tab = typename std::conditional<INS, typename Env::RecTabWide, typename Env::RecTab>::type;
+    using Entry = typename std::conditional<INS, u32x4, uint2>::type;
+    __shared__ Tab tab;
     const uint32_t n_act = (uint32_t)Env::n_actions(p);
     // a quad per thread on a tape: the loop unrolled by two, the tape read two steps ahead (TapeQuadAhead)
     constexpr bool AHEAD2 = Pol::TAPE && LPT == 4;
@@ -420,20 +425,23 @@ __device__ __forceinline__ void steps_quad_body(uint32_t *__restrict__ state, in
         cx.first(gen_first, a_cur);
 #pragma unroll
         for (int j = 0; j < LPT; ++j) {
-            if constexpr (INS) st[j].s = (s_lo[j] << Env::ROT_POS) | ((s_lo[j] >> (8u - Env::INS_ROCK0)) & (0xFFFFu << Env::INS_ROCK0));
+            if constexpr (INS) st[j].s = Env::wide_from_mem(s_lo[j]);
             else if constexpr (ROT) st[j].s = __builtin_amdgcn_alignbit(s_lo[j], s_lo[j], 8u);
             else st[j].s = (S)((uint64_t)s_lo[j] | ((uint64_t)s_hi[j] << 32));
         }
     }
     Env::stage(sh, p, (int)threadIdx.x);
     __syncthreads();
-    Env::template build_rec_tab<ROT, INS>(tab, sh, p, (int)threadIdx.x);
+    if constexpr (INS) {
+        if (threadIdx.x < (unsigned)Env::WIDE_SLOTS) Env::build_rec_tab_wide(tab, sh, p, (int)threadIdx.x);
+    } else Env::template build_rec_tab<ROT>(tab, sh, p, (int)threadIdx.x);
     __syncthreads();
     const int K = p.num_rocks;
     const uint32_t start = (uint32_t)p.start_x | ((uint32_t)p.start_y << 4);
     // ... where the rotated layout has it, in a vector register: (H & codes) | start is then one v_and_or_b32 (two scalar
     // operands do not fit one instruction)
     uint32_t start_rot = start << (ROT ? Env::ROT_POS : 0u);
+    if constexpr (INS) start_rot = Env::wide_start(start);
     if constexpr (ROT) asm volatile("" : "+v"(start_rot));
     const LoopPrio prio(k_steps);
     constexpr uint32_t SENSOR_BLOCK = Env::SENSOR_BLOCK;
@@ -489,11 +497,18 @@ __device__ __forceinline__ void steps_quad_body(uint32_t *__restrict__ state, in
             // for the lanes whose sensor draw the high word may leave undecided (H - e < TIE_SPAN; 2^-27 per CHECK), then every
             // compare and the records
             uint32_t fresh[LPT], sn[LPT];
-            uint2 ef[LPT];
+            Entry ef[LPT];
             Env::template fresh_states<LPT, true, NUMERIC, INS>(H, key, glane0, K, start_rot, tie_bound, fresh);
 #pragma unroll
-            for (int j = 0; j < LPT; ++j) ef[j] = Env::template rec_lookup<true, INS>(tab, st[j].s, valid[j] ? a_taken[j] : 0u);
-            {   // all of them have landed: one wait (each entry passes as the register pair its read filled: no copies)
+            for (int j = 0; j < LPT; ++j) {
+                if constexpr (INS) ef[j] = Env::rec_lookup_wide(tab, st[j].s, valid[j] ? a_taken[j] : 0u);
+                else ef[j] = Env::template rec_lookup<true>(tab, st[j].s, valid[j] ? a_taken[j] : 0u);
+            }
+            // all of them have landed: one wait (each entry passes as the register tuple its read filled: no copies)
+            if constexpr (INS) {
+                if constexpr (LPT == 4) asm volatile("" : "+v"(ef[0]), "+v"(ef[1]), "+v"(ef[2]), "+v"(ef[3]));
+                else asm volatile("" : "+v"(ef[0]), "+v"(ef[1]));
+            } else {
                 uint64_t w[LPT];
 #pragma unroll
                 for (int j = 0; j < LPT; ++j) w[j] = (uint64_t)ef[j].x | ((uint64_t)ef[j].y << 32);
@@ -513,13 +528,16 @@ __device__ __forceinline__ void steps_quad_body(uint32_t *__restrict__ state, in
             if (nearest < Env::TIE_SPAN) {
 #pragma unroll
                 for (int j = 0; j < LPT; ++j)
-                    if (near[j] < Env::TIE_SPAN)
-                        correct[j] = Env::template rec_sensor_exact<true, INS>(sh, st[j].s, ef[j].y, H[j], [&]() { return low_word(j); });
+                    if (near[j] < Env::TIE_SPAN) {
+                        if constexpr (INS) correct[j] = Env::rec_sensor_exact_wide(sh, st[j].s, ef[j].y, H[j], [&]() { return low_word(j); });
+                        else correct[j] = Env::template rec_sensor_exact<true>(sh, st[j].s, ef[j].y, H[j], [&]() { return low_word(j); });
+                    }
             }
 #pragma unroll
             for (int j = 0; j < LPT; ++j) {
                 sn[j] = st[j].s;
-                Env::template rec_finish<INS>(ef[j], sn[j], valid[j] ? a_taken[j] : 0u, correct[j], fresh[j], rec[j]);
+                if constexpr (INS) Env::rec_finish_wide(ef[j], sn[j], correct[j], fresh[j], rec[j]);
+                else Env::rec_finish(ef[j], sn[j], valid[j] ? a_taken[j] : 0u, correct[j], fresh[j], rec[j]);
             }
 #pragma unroll
             for (int j = 0; j < LPT; ++j) {
@@ -581,8 +599,8 @@ __device__ __forceinline__ void steps_quad_body(uint32_t *__restrict__ state, in
 #pragma unroll
     for (int j = 0; j < LPT; ++j) {
         const uint32_t sj = (uint32_t)st[j].s;
-        w_lo[j] = INS ? (sj >> Env::ROT_POS) | ((sj & (0xFFFFu << Env::INS_ROCK0)) << (8u - Env::INS_ROCK0))
-                      : ROT ? __builtin_amdgcn_alignbit(sj, sj, 24u) : sj;
+        if constexpr (INS) w_lo[j] = Env::wide_to_mem(sj);
+        else w_lo[j] = ROT ? __builtin_amdgcn_alignbit(sj, sj, 24u) : sj;
     }
     if constexpr (LPT == 4) {
         st_stream4(state + l0, w_lo[0], w_lo[1], w_lo[2], w_lo[3]);
@@ -1397,8 +1415,10 @@ static int launch_steps_fused_l(const typename Env::Params &p, uint32_t *state, 
                 snprintf(pname, sizeof pname, "%s, 2", lname);
                 note_fused("steps_quad_kernel", Env::NAME, pname);
                 // (one state word: the reset-tie filter by number or by popcount, RockEnv::fresh_states — the same loop otherwise)
+                // (... and the 16-byte table entries' three-bit coordinates want a side of at most RockEnv::WIDE_SIDE: every
+                // reference board with at most eight rocks has one)
                 bool popc = false;
-                if constexpr (Env::WORDS == 1) popc = p.num_rocks > Env::RESET_NUMERIC_K;
+                if constexpr (Env::WORDS == 1) popc = p.num_rocks > Env::RESET_NUMERIC_K || p.size > Env::WIDE_SIDE;
                 if constexpr (Env::WORDS == 1) { if (popc) POMDP_LAUNCH_PAIR(steps_quad_popc_kernel<Env, L); }
                 if (!popc) POMDP_LAUNCH_PAIR(steps_quad_kernel<Env, L);
                 launched = true;
@@ -1407,7 +1427,7 @@ static int launch_steps_fused_l(const typename Env::Params &p, uint32_t *state, 
         if (!launched && quad_ok && n >= (Env::STOCHASTIC ? QUAD_MIN_STOCHROCK : QUAD_MIN_ROCK) && k >= 16 && p.num_rocks + 5 <= Env::TAB_ACTIONS) {
             note_fused("steps_quad_kernel", Env::NAME, lname);
             bool popc = false;
-            if constexpr (Env::WORDS == 1) popc = p.num_rocks > Env::RESET_NUMERIC_K;
+            if constexpr (Env::WORDS == 1) popc = p.num_rocks > Env::RESET_NUMERIC_K || p.size > Env::WIDE_SIDE;
             if constexpr (Env::WORDS == 1) { if (popc) POMDP_LAUNCH_QUAD(steps_quad_popc_kernel<Env, L); }
             if (!popc) POMDP_LAUNCH_QUAD(steps_quad_kernel<Env, L);
             launched = true;

@@ -140,7 +140,9 @@ def is_tie_path(prev, b, out_of_line=()):
     if not masked and b["label"] not in out_of_line:
         return False
     v = [i for i in b["insts"] if i.startswith("v_")]
-    return len(v) >= 30 and sum(base(i) in PHILOX_OPS for i in v) >= 0.6 * len(v)
+    # (half: the quad loops' tie path on 16-byte entries takes the position from two three-bit fields and the rock slot from the
+    # mask word before its block, 31 to 34 Philox instructions among 53 to 57; every other tie path is above 0.7)
+    return len(v) >= 30 and sum(base(i) in PHILOX_OPS for i in v) >= 0.5 * len(v)
 
 
 def loop_key(b):
