@@ -200,51 +200,28 @@ struct RockEnv {
             for (int e = 0; e < 4; ++e) codes[e] = reset_codes<true>(R[e], key, first + (uint32_t)e, K);
         }
     }
-    // The fresh episodes a step may hand the N lanes of one thread (N = 4: the quad first .. first + 3, N = 2: half of it), as
-    // state words (one state word; ROT: in the rotated layout of build_rec_tab<true>) from the lanes' words R of the step's
-    // sensor block; `start`: the start cell's position byte where the layout has it.  ONE branch for the ties; off it a lane
-    // costs one v_and_or_b32 (ROT, `start` in a vector register) — the codes stay where the word has them.
-    // What sends a thread into the branch: rock j ties only if the word rotated right by 2 j + 2 lies in [2^31, 2^31 + 32),
-    // i.e. bits 2 j + 7 .. 2 j + 32 of the word, taken cyclically, are zero.  For every j < K those ranges share bits
-    // 2 K + 5 .. 31, so with 2 K + 5 < 32 a tie needs word < 2^(2 K + 5) = reset_tie_bound(K).  NUMERIC (the caller's choice
-    // per launch, for K <= RESET_NUMERIC_K): the filter is the smallest of the thread's words against `bound` (2^-11 per lane
-    // at K = 8) and no bit is counted off the branch.  Above, the bound passes too many lanes (one in 32 at K = 11) and the
-    // filter is the popcount test itself.
-    // INS (with ROT, K <= RESET_NUMERIC_K): the layout of build_rec_tab_wide, rock 0's code at bit INS_ROCK0 — the word
-    // shifted up by that, then the same v_and_or_b32 (`start`: wide_start).
+    // The fresh episodes a step may hand the N lanes of one thread (N = 4: the quad first .. first + 3, N = 2: half of it) from
+    // the lanes' words R of the step's sensor block (auto-reset): out[e] = rock j's code at bit ROCK0 + 2 j, or-ed onto
+    // `start` (what else the caller's word holds).  ONE branch for the ties (fresh_ties); off it a lane
+    // costs one v_and_or_b32 where ROCK0 = 0 and `start` is in a vector register — the codes stay where the word has them —
+    // and a shift more elsewhere.
+    // What sends a thread into the branch is the form's filter.  Rock j ties only if the word rotated right by
+    // 2 j + 2 lies in [2^31, 2^31 + 32), i.e. bits 2 j + 7 .. 2 j + 32 of the word, taken cyclically, are zero.  For every
+    // j < K those ranges share bits 2 K + 5 .. 31, so with 2 K + 5 < 32 a tie needs word < 2^(2 K + 5).  RecWide, for
+    // K <= RESET_NUMERIC_K: the smallest of the thread's words against that bound (2^-11 per lane at K = 8), no bit counted off
+    // the branch.  Above, the bound passes too many lanes (one in 32 at K = 11): Rec8's filter is the popcount test itself.
     static constexpr int RESET_NUMERIC_K = 8;
-    static constexpr uint32_t INS_ROCK0 = 5u;
-    static __device__ __forceinline__ uint32_t reset_tie_bound(int K) { return 1u << (2 * min(K, RESET_NUMERIC_K) + 5); }
-    template <int N, bool ROT, bool NUMERIC, bool INS = false>
-    static __device__ __forceinline__ void fresh_states(const uint32_t (&R)[N], const RngKey &key, uint32_t first, int K,
-                                                        uint32_t start, uint32_t bound, uint32_t (&fresh)[N])
+    template <int N, int ROCK0> static __device__ __forceinline__ void fresh_words(const uint32_t (&R)[N], int K, uint32_t start, uint32_t (&out)[N])
     {
-        static_assert(!INS || (ROT && NUMERIC), "the insert layout is the rotated one of the boards with at most RESET_NUMERIC_K rocks");
         const uint32_t exist = K >= 16 ? 0xFFFFFFFFu : ((1u << (2 * K)) - 1u);
-        constexpr int ROCK0 = INS ? (int)INS_ROCK0 : ROT ? 0 : 8;
-        auto word = [&](uint32_t codes) { return ROT ? (codes | start) : (start | (codes << 8)); };
 #pragma unroll
-        for (int e = 0; e < N; ++e) {
-            if constexpr (INS) fresh[e] = ((R[e] << INS_ROCK0) & ((0xAAAAAAAAu & exist) << INS_ROCK0)) | start;
-            else fresh[e] = word(R[e] & (0xAAAAAAAAu & exist));
-        }
-        bool look;
-        if constexpr (NUMERIC) {
-            uint32_t least = R[0];
+        for (int e = 0; e < N; ++e) out[e] = ((R[e] << ROCK0) & ((0xAAAAAAAAu & exist) << ROCK0)) | start;
+    }
+    template <int N, int ROCK0> static __device__ __forceinline__ void fresh_ties(const uint32_t (&R)[N], const RngKey &key, uint32_t first, int K, uint32_t (&out)[N])
+    {
 #pragma unroll
-            for (int e = 1; e < N; ++e) least = min(least, R[e]);
-            look = least < bound;
-        } else {
-            int fewest = __popc(R[0]);
-#pragma unroll
-            for (int e = 1; e < N; ++e) fewest = min(fewest, (int)__popc(R[e]));
-            look = fewest <= 6;
-        }
-        if (look) {
-#pragma unroll
-            for (int e = 0; e < N; ++e)
-                if (__popc(R[e]) <= 6) reset_ties<true>(R[e], key, first + (uint32_t)e, K, fresh[e], ROCK0);
-        }
+        for (int e = 0; e < N; ++e)
+            if (__popc(R[e]) <= 6) reset_ties<true>(R[e], key, first + (uint32_t)e, K, out[e], ROCK0);
     }
     // rock.py:236-241 reset -> 266-271 _get_init_state -> 78-86 Rock.__init__:
     // status_j = sign(U_j - .5), rocks in index order, one double each.
@@ -497,18 +474,19 @@ struct RockEnv {
         return sh.thr[__builtin_amdgcn_sad_u8(x | (y << 8), sh.rpos[r & 15], 0u)].y;
     }
     static constexpr int TAB_ACTIONS = W == 1 ? 17 : 21;                    // 5 + K: K <= 12 in one state word, <= 16 in two
+    // the board's actions fit the tables below: what every table-driven launch asks first
+    static __host__ __device__ __forceinline__ bool tab_ok(const Params &p) { return 5 + p.num_rocks <= TAB_ACTIONS; }
 
     // ---- the lane step from a (position, action) -> outcome table, as one packed record -------------------------------------
     // Everything a step derives from the agent's cell and the action alone — where a move leads and whether it leaves the
-    // board, which rock lies under a SAMPLE, the sensor threshold of a CHECK from here — is one 32-bit entry, built in LDS by
-    // the workgroup when a multi-step launch starts (one thread per cell, one pass over the actions) and read with a single
-    // lookup per lane-step.  With 4-byte trajectory records the fused loops are bound by instruction issue; a lane step that
-    // fills (reward, done, aux) for a separate sensor / select stage cost ~49 vector instructions (round 3's step_tab, gone
-    // since every table-driven launch takes this form).  step_rec produces the lane's Packed record
-    // (traj_out.hip.h: action | ob << 8 | reward code << 16 | done << 24) and its new state in 20 with one state word (measured
-    // in the quad loop's gfx950 code; 27 until the entry held the record's bytes), from a table whose entries already hold, per
-    // (action, position), everything that does not depend on the rocks' codes:
-    // Two state words (4-byte entries):
+    // board, which rock lies under a SAMPLE, the sensor threshold of a CHECK from here — is one table entry, built in LDS by
+    // the workgroup when a multi-step launch starts and read with a single lookup per lane-step.  With 4-byte trajectory
+    // records the fused loops are bound by instruction issue: the lane step produces the lane's Packed record
+    // (traj_out.hip.h: action | ob << 8 | reward code << 16 | done << 24) and its new state from an entry that already holds,
+    // per (action, position), everything that does not depend on the rocks' codes.
+    // Outcome codes: 0 = bad rock sampled (-10), 1 = penalty (-100, done), 2 = good rock sampled (+10), 3 = east exit (+10,
+    // done), 6 = nothing (0) — a sampled rock's own code IS its outcome code, done is bit 0.
+    // Two state words (4-byte entries; 21 x 256 x 8 = 42 KB would leave three workgroups per CU):
     //   every entry: bits 28-30 = the OUTCOME CODE the step has when no uncollected rock is sampled ("fallback"), bit 31 =
     //                a rock with an id < K lies under a SAMPLE;
     //   a <  4: bits 0-7 = position byte XOR new position byte (0 if the move leaves); fallback 6 inside, 3 leaving east,
@@ -520,72 +498,32 @@ struct RockEnv {
     //           v_alignbit_b32), so the threshold test and the tie test read the entry as it is;
     //   a <  5: bit 27 set.  (H >> 5) | 6 << 28 has bit 27 clear, so only a CHECK's entry can tie with it: the tie test needs
     //           no test of the action.
-    // Outcome codes: 0 = bad rock sampled (-10), 1 = penalty (-100, done), 2 = good rock sampled (+10), 3 = east exit (+10,
-    // done), 6 = nothing (0) — a sampled rock's own code IS its outcome code, done is bit 0.
-    // One state word (K <= 12): the entry is 8 bytes, read with one ds_read_b64 (17 x 256 x 8 = 34 KB of LDS per workgroup,
-    // four workgroups per CU fit).  The first word is what the lane's RAW sensor word H compares with:
-    //   a >= 5: E = T << 5 with T = thr >> 26 the threshold's high part at this distance, saturated to 0xFFFFFFFF where
-    //           T = 2^27 (a sensor that is always right at distance 0).  `correct` = H < E is (H >> 5) < T exactly for every
-    //           T < 2^27, and the draw the high word leaves undecided, (H >> 5) == T, is H - E < 32 (unsigned);
-    //   a <  5: 0xFFFFFFFF (`correct` is not used).
-    // H - E < 32 is a FILTER: against a saturated or a non-CHECK entry it also passes H = 0xFFFFFFFF and, wrapping, H < 31
-    // (2^-27 per lane-step); the rare path behind it (rec_sensor_exact) recomputes the draw from the threshold itself,
-    // (H >> 5) against T and the low word on equality.
-    // The second word is the fallback's record in its final place, and where the state changes:
-    //   bit 31     = a rock with an id < K lies under a SAMPLE (REC_ROCK; rec_finish masks it out of the record);
-    //   bits 16-23 = the fallback's reward byte, bit 24 = its done bit: the record's upper half as it is stored;
-    //   bits 8-9   = 3 in a CHECK's entry, else 0: the record's ob field keeps bit 9 if the reading matches the rock, else
-    //                bit 8 (one select between two masks, one v_and_or_b32 that also puts the action in);
-    //   bits 0-4   = a bit offset `off` into the state word, bits 5-6 = a signed step c in {-1, 0, +1}: the new state is
-    //                s + (c << off).  A move: off = 0 (x) or 4 (y), c = the direction, 0 if it leaves (no carry leaves the
-    //                nibble of a move that stays inside).  SAMPLE and CHECK: off = where the code of the rock underfoot / of the
-    //                measured rock lies, c = 0 — one v_bfe_u32 reads that code q for both: a CHECK's rock is good iff q == 2; a
-    //                SAMPLE with a rock underfoot and q != 1 collects it, code -> 1, which is the step c = 1 - q at the same
-    //                offset, and its record is 0x00F60004 - q * 0x00760000 (reward byte 0xF6 = -10 or 0x0A = +10, action 4).
-    // done is read off the finished record (>= 1 << 24).
-    // The quad-per-thread loops (steps_quad_kernel) take the step in its two halves — rec_lookup for all of a thread's lanes, one
-    // wait, one v_sub_co_u32 per lane (H - e for the filter; its borrow IS `correct`), ONE branch for the lanes the filter passes,
-    // rec_finish — and keep the state word rotated right by 8 in
-    // registers (ROT: rock j's code at bit 2 j, the position byte on top; one v_alignbit_b32 per lane after the launch's load
-    // and one before its store): the entry's address is one v_alignbit_b32 and one v_and_b32 (a << 11 | position << 3), and a
-    // fresh episode one v_and_or_b32 of the lane's sensor word — its rocks' codes are where the word has them — instead of a
-    // v_and_b32 and a v_lshl_or_b32: 17 + 1 vector instructions per lane-step there and three per thread for the filter
-    // (v_min_u32, v_min3_u32, one compare).  The table differs in its bit offsets only (build_rec_tab<true>).
-    // With at most RESET_NUMERIC_K = 8 rocks (INS, steps_quad_kernel) the entry is 16 bytes (RecTabWide, build_rec_tab_wide
-    // below) and holds the insert mask and both finished records ready-made: the state half of the step is one v_bfi_b32, the
-    // record one v_cndmask_b32 between two words of the entry — 12 vector instructions per lane-step (v_alignbit_b32,
-    // v_sub_co_u32, v_bfe_u32, three compares of q and the flag, v_cndmask_b32, v_mad_i32_i24, v_cndmask_b32, v_bfi_b32, the
-    // done compare, v_cndmask_b32) and 2 for the fresh episode.  steps_quad_popc_kernel (9 to 12 rocks) keeps 17 + 1.
-    // Two state words keep 4-byte entries (21 x 256 x 8 = 42 KB would leave three workgroups per CU), test the action, and
-    // look the reward byte up by outcome code with one v_perm_b32 in an 8-byte constant; that branch is as it was.
-    static constexpr uint32_t REC_LUT_LO = 0x0A0A9CF6u, REC_LUT_HI = 0x00000000u;   // reward byte by outcome code 0..7 (two state words)
+    // step_rec tests the action and looks the reward byte up by outcome code with one v_perm_b32 in an 8-byte constant.
+    // One state word (K <= 12): three forms of (state word in registers, table entry) — RecMem, RecRot, RecWide below.  Memory
+    // always keeps x | y << 4 | codes << 8.  Each form has the lane step in its two halves, for the loops that issue the table
+    // reads of all of a thread's lanes before they use the first (steps_quad_body): `lookup` reads the entry; the lane's RAW
+    // sensor word H compares with the entry's first word `cmp` — `correct` = H < cmp, and H - cmp < TIE_SPAN is a FILTER for the
+    // draws the high word leaves undecided: `exact` decides those from the threshold itself — and `finish` makes the record and
+    // the new state.  `settle` is the one wait between the halves, `fresh` the fresh episodes in the form's layout.
+    static constexpr uint32_t REC_LUT_LO = 0x0A0A9CF6u, REC_LUT_HI = 0x00000000u;   // reward byte by outcome code 0..7
     using TabEntry = typename std::conditional<W == 1, uint2, uint32_t>::type;
     struct RecTab { TabEntry e[TAB_ACTIONS][256]; };
-    static constexpr uint32_t REC_ROCK = 1u << 31;           // second word of a one-state-word entry: a rock lies under this SAMPLE
-    static constexpr uint32_t TIE_SPAN = 32u;                // H - E below this: the high word may leave the draw undecided
-    // first word of a one-state-word CHECK entry from the threshold's high part T = thr >> 26 <= 2^27
-    // (INS: the saturated word keeps its low five bits clear — a wide entry's mask word has the rock's bit offset there, and no
-    // state bit may come from under it — and every H from 0xFFFFFFE0 up passes the filter instead: rec_sensor_exact_wide finds
-    // (H >> 5) < 2^27 = T, correct, as it must be)
-    template <bool INS = false>
-    static __device__ __forceinline__ uint32_t rec_thr_word(uint32_t T) { return T >= (1u << 27) ? (INS ? 0xFFFFFFE0u : 0xFFFFFFFFu) : T << 5; }
-    // second word of a one-state-word entry: step `c` (-1, 0, +1) at bit offset `off`, ob mask, the record's reward byte and done bit
+    static constexpr uint32_t REC_ROCK = 1u << 31;           // a rock with an id < K lies under this SAMPLE
+    static constexpr uint32_t TIE_SPAN = 32u;                // H - cmp below this: the high word may leave the draw undecided
+    // second word of an 8-byte entry: step `c` (-1, 0, +1) at bit offset `off`, ob mask, the record's reward byte and done bit
     static __device__ __forceinline__ uint32_t rec_f(uint32_t off, int c, uint32_t ob_mask, uint32_t oc)
     {
         const uint32_t rbyte = (((uint64_t)REC_LUT_HI << 32 | REC_LUT_LO) >> (8u * oc)) & 0xFFu;
         return off | (((uint32_t)c & 3u) << 5) | (ob_mask << 8) | (rbyte << 16) | ((oc & 1u) << 24);
     }
-    // ROT: the table of a loop that keeps the state word rotated right by 8 in registers (steps_quad_kernel, one state word):
-    // rock j's code at bit 2 j, the position byte on top at bits 24-31 (ROT_POS).  The entries are the same but for their bit
-    // offsets: a move's 24 (x) or 28 (y), a rock's 2 j.  No step carries out of its field in either layout: a move that stays
-    // inside keeps its nibble (and y is the word's top nibble), and a SAMPLE takes a code of 0 or 2 to 1 — + 1 on 0, - 1 on 2,
-    // neither leaves the two bits — so the last rock of a 12-rock board, at bits 22-23 right under x, never reaches the position.
-    static constexpr uint32_t ROT_POS = 24u;
-    template <bool ROT = false>
+    // first word of an 8-byte CHECK entry from the threshold's high part T = thr >> 26 <= 2^27 (Rec8 below)
+    static __device__ __forceinline__ uint32_t rec_thr_word(uint32_t T) { return T >= (1u << 27) ? 0xFFFFFFFFu : T << 5; }
+    // The entries of cell `pos` (one thread per position byte): e = the 4-byte entry of two state words; one state word: the
+    // 8-byte entry of Rec8<POS0> below — x at bit POS0, rock 0's code at bit ROCK0 — and f its second word.
+    template <uint32_t POS0 = 0u>
     static __device__ __forceinline__ void build_rec_tab(RecTab &tab, const Shared &sh, const Params &p, int pos)
     {
-        static_assert(!ROT || W == 1, "the rotated layout is the one-state-word loops'");
-        constexpr uint32_t POS0 = ROT ? ROT_POS : 0u, ROCK0 = ROT ? 0u : 8u;     // bit offsets of x and of rock 0's code
+        constexpr uint32_t ROCK0 = (POS0 + 8u) & 31u;
         const uint32_t x = (uint32_t)pos & 15u, y = (uint32_t)pos >> 4, size = (uint32_t)p.size, K = (uint32_t)p.num_rocks;
         const int id = sh.grid[x * 16 + y];
         const uint32_t NOTHING = 6u << 28, PENALTY = (STOCH ? 6u : 1u) << 28, EXIT_EAST = 3u << 28;
@@ -611,36 +549,8 @@ struct RockEnv {
             else tab.e[a][pos] = e;
         }
     }
-    // rock.py:123-194 for one lane: s -> s' (the fresh episode `fresh` if the step ends this one), rec = the step's record.
-    // H: the lane's sensor high word; `lo` yields its low word (a tie, 2^-27 per CHECK).  Two state words (K > 12): the rock
-    // codes run on into the upper word (rock j at bits 8 + 2 j), a code never straddles the words, and the word a SAMPLE or
-    // a CHECK reads is a select on bit 5 of its bit offset.
-    // The one-state-word lane step in its two halves, for the loops that issue the table reads of all of a thread's lanes before
-    // they use the first (steps_quad_kernel): rec_lookup reads the entry, the raw sensor word compares with its first word
-    // (`correct` = H < e; H - e < TIE_SPAN: rec_sensor_exact decides instead), rec_finish makes the record and the new state.
-    // ROT: the state word is kept rotated (build_rec_tab<true>).
-    template <bool ROT = false>
-    static __device__ __forceinline__ uint2 rec_lookup(const RecTab &tab, uint32_t s, uint32_t a)
-    {
-        if constexpr (ROT) {
-            // the entry's byte offset a << 11 | position << 3 in one v_alignbit_b32 (the position byte is the word's top) and one
-            // v_and_b32 that clears the three code bits that came along
-            const uint32_t off = __builtin_amdgcn_alignbit(a, s, ROT_POS - 3u) & ~7u;
-            return *reinterpret_cast<const uint2 *>(reinterpret_cast<const char *>(&tab.e[0][0]) + off);
-        } else return tab.e[a][s & 0xFFu];
-    }
-    // The sensor draw of a lane the filter H - e < TIE_SPAN passed, from the threshold itself: (H >> 5) against T, the low word
-    // against the threshold's low 26 bits where they are equal (2^-27 per CHECK).  The measured rock is read off the entry's
-    // offset, not the action, so that a tape-driven loop's rare path does not keep a tape row it wants to load over alive.  The
-    // filter also passes H = 0xFFFFFFFF and H < 31 on a move or a SAMPLE: their offsets name some rock slot below 16, every
-    // read stays inside its table, and rec_finish does not use `correct` for them.
-    template <bool ROT = false, class LowWord>
-    static __device__ __forceinline__ bool rec_sensor_exact(const Shared &sh, uint32_t s, uint32_t f, uint32_t H, LowWord lo)
-    {
-        const uint32_t pos = ROT ? s >> ROT_POS : s, r = (((f & 31u) - (ROT ? 0u : 8u)) >> 1) & 15u;
-        return sensor_exact_at(sh, (pos & 15u) | ((pos & 0xF0u) << 4), r, H, lo);
-    }
-    // ... at the agent's bytes `xy` = x | y << 8, for rock slot r < 16
+    // The sensor draw of a lane the filter passed, from the threshold itself, at the agent's bytes `xy` = x | y << 8 for rock
+    // slot r < 16: (H >> 5) against T, the low word against the threshold's low 26 bits where they are equal (2^-27 per CHECK).
     template <class LowWord>
     static __device__ __forceinline__ bool sensor_exact_at(const Shared &sh, uint32_t xy, uint32_t r, uint32_t H, LowWord lo)
     {
@@ -652,133 +562,246 @@ struct RockEnv {
         asm volatile("" : "+v"(kl));
         return kh == t.x ? kl <= t.y : kh < t.x;
     }
-    static __device__ __forceinline__ void rec_finish(const uint2 ef, uint32_t &s, uint32_t a, bool correct, uint32_t fresh, uint32_t &rec)
-    {
-        const uint32_t f = ef.y;
-        // the code of the rock this step is about — under a SAMPLE, or the one a CHECK measures — read at the entry's offset
-        // (a move's entry points at the position nibble it changes: whatever this reads there is not used)
-        const uint32_t q = __builtin_amdgcn_ubfe(s, f, 2u);
-        const bool ok = ((int32_t)f < 0) & (q != 1u);                       // SAMPLE: an uncollected rock with an id < K is underfoot (REC_ROCK)
-        // the record when no live rock is sampled: the entry's own bytes without REC_ROCK, of its two ob bits the one the
-        // reading gives (CHECK rock a - 5, rock.py:171-175, 401-407: good = its code is 2)
-        const uint32_t keep = ((q == 2u) == correct) ? 0x7FFFFE00u : 0x7FFFFD00u;
-        const uint32_t rfb = (f & keep) | a;
-        // a sampled rock's code IS its outcome: 0 -> -10 (0xF6), 2 -> +10 (0x0A), never done; the action byte is SAMPLE's
-        const uint32_t rok = 0x00F60004u - q * 0x00760000u;
-        rec = ok ? rok : rfb;
-        // the state moves by a step of -1, 0 or +1 at the entry's offset: a move's nibble, or a sampled rock's code -> 1
-        const int c = ok ? 1 - (int)q : __builtin_amdgcn_sbfe((int)f, 5u, 2u);
-        const uint32_t moved = s + ((uint32_t)c << (f & 31u));
-        s = rec >= (1u << 24) ? fresh : moved;                              // done: byte 3 of the finished record
-    }
-    // ---- 16-byte entries (INS: steps_quad_kernel, one state word, at most RESET_NUMERIC_K = 8 rocks) ---------------------------
-    // Every board with at most eight rocks has a side of at most 7 (RockSample(7,8), (7,7), (4,3), (2,1)): a coordinate is three
+
+    // 8-byte entries, one ds_read_b64 (17 x 256 x 8 = 34 KB of LDS per workgroup, four workgroups per CU fit), for a state word
+    // that is the memory word rotated left by POS0: x at bit POS0, y above it, rock j's code at bit ROCK0 + 2 j.
+    //   RecMem = Rec8<0>:        the memory layout itself (step_rec: steps_kernel, rollout_kernel, episodes_quad_kernel);
+    //   RecRot = Rec8<ROT_POS>:  rotated right by 8 — rock j's code at bit 2 j, the position byte on top — so that a fresh
+    //                            episode is one v_and_or_b32 of the lane's sensor word and the entry's address one
+    //                            v_alignbit_b32 and one v_and_b32 (steps_quad_popc_kernel: 9 to 12 rocks, or a side above 7).
+    // The entries are the same but for their bit offsets.  No step carries out of its field in either layout: a move that stays
+    // inside keeps its nibble (and in RecRot y is the word's top nibble), and a SAMPLE takes a code of 0 or 2 to 1 — + 1 on 0,
+    // - 1 on 2, neither leaves the two bits — so the last rock of a 12-rock board, in RecRot at bits 22-23 right under x, never
+    // reaches the position.
+    // The first word is what H compares with:
+    //   a >= 5: E = T << 5 with T = thr >> 26 the threshold's high part at this distance, saturated to 0xFFFFFFFF where
+    //           T = 2^27 (a sensor that is always right at distance 0).  `correct` = H < E is (H >> 5) < T exactly for every
+    //           T < 2^27, and the draw the high word leaves undecided, (H >> 5) == T, is H - E < 32 (unsigned);
+    //   a <  5: 0xFFFFFFFF (`correct` is not used).
+    // Against a saturated or a non-CHECK entry the filter also passes H = 0xFFFFFFFF and, wrapping, H < 31 (2^-27 per
+    // lane-step); `exact` recomputes the draw whatever sent the lane there.
+    // The second word is the fallback's record in its final place, and where the state changes:
+    //   bit 31     = REC_ROCK (finish masks it out of the record);
+    //   bits 16-23 = the fallback's reward byte, bit 24 = its done bit: the record's upper half as it is stored;
+    //   bits 8-9   = 3 in a CHECK's entry, else 0: the record's ob field keeps bit 9 if the reading matches the rock, else
+    //                bit 8 (one select between two masks, one v_and_or_b32 that also puts the action in);
+    //   bits 0-4   = a bit offset `off` into the state word, bits 5-6 = a signed step c in {-1, 0, +1}: the new state is
+    //                s + (c << off).  A move: off = x's or y's, c = the direction, 0 if it leaves.  SAMPLE and CHECK: off =
+    //                where the code of the rock underfoot / of the measured rock lies, c = 0 — one v_bfe_u32 reads that code q
+    //                for both: a CHECK's rock is good iff q == 2; a SAMPLE with a rock underfoot and q != 1 collects it, code
+    //                -> 1, which is the step c = 1 - q at the same offset, and its record is 0x00F60004 - q * 0x00760000
+    //                (reward byte 0xF6 = -10 or 0x0A = +10, action 4).
+    // done is read off the finished record (>= 1 << 24).
+    static constexpr uint32_t ROT_POS = 24u;
+    template <uint32_t POS0>
+    struct Rec8 {
+        static_assert(POS0 == 0u || POS0 == ROT_POS, "the memory layout, or the position byte on top");   // (two state words: Tab alone)
+        static constexpr uint32_t ROCK0 = (POS0 + 8u) & 31u;
+        using Tab = RecTab;
+        using Entry = uint2;
+        static __device__ __forceinline__ uint32_t from_mem(uint32_t m) { return __builtin_amdgcn_alignbit(m, m, (32u - POS0) & 31u); }
+        static __device__ __forceinline__ uint32_t to_mem(uint32_t s) { return __builtin_amdgcn_alignbit(s, s, POS0); }
+        // the start cell (x | y << 4) where this layout has the position: what `fresh` ors the codes onto
+        static __device__ __forceinline__ uint32_t start_word(uint32_t start) { return start << POS0; }
+        // one thread per position byte: the whole workgroup
+        static __device__ __forceinline__ bool builds(uint32_t) { return true; }
+        static __device__ __forceinline__ void build(Tab &tab, const Shared &sh, const Params &p, int tid) { build_rec_tab<POS0>(tab, sh, p, tid); }
+        static __device__ __forceinline__ Entry lookup(const Tab &tab, uint32_t s, uint32_t a)
+        {
+            if constexpr (POS0 == ROT_POS) {
+                // the entry's byte offset a << 11 | position << 3 in one v_alignbit_b32 (the position byte is the word's top) and
+                // one v_and_b32 that clears the three code bits that came along
+                const uint32_t off = __builtin_amdgcn_alignbit(a, s, ROT_POS - 3u) & ~7u;
+                return *reinterpret_cast<const uint2 *>(reinterpret_cast<const char *>(&tab.e[0][0]) + off);
+            } else return tab.e[a][s & 0xFFu];
+        }
+        // all N entries have landed: one wait.  (Each passes as the 64-bit register pair its read filled: no copies.)
+        template <int N> static __device__ __forceinline__ void settle(Entry (&ef)[N])
+        {
+            uint64_t w[N];
+#pragma unroll
+            for (int j = 0; j < N; ++j) w[j] = (uint64_t)ef[j].x | ((uint64_t)ef[j].y << 32);
+            if constexpr (N == 4) asm volatile("" : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]));
+            else asm volatile("" : "+v"(w[0]), "+v"(w[1]));
+#pragma unroll
+            for (int j = 0; j < N; ++j) ef[j] = make_uint2((uint32_t)w[j], (uint32_t)(w[j] >> 32));
+        }
+        static __device__ __forceinline__ uint32_t cmp(const Entry ef) { return ef.x; }
+        // The measured rock is read off the entry's offset, not the action, so that a tape-driven loop's rare path does not keep
+        // a tape row it wants to load over alive.  On a move or a SAMPLE the filter let through, the offset names some rock slot
+        // below 16, every read stays inside its table, and `finish` does not use `correct` for them.
+        template <class LowWord> static __device__ __forceinline__ bool exact(const Shared &sh, uint32_t s, const Entry ef, uint32_t H, LowWord lo)
+        {
+            const uint32_t pos = s >> POS0, r = (((ef.y & 31u) - ROCK0) >> 1) & 15u;
+            return sensor_exact_at(sh, (pos & 15u) | ((pos & 0xF0u) << 4), r, H, lo);
+        }
+        // `act` yields the action: asked once, first, by the form whose entry does not hold the action byte
+        template <class Act> static __device__ __forceinline__ void finish(const Entry ef, uint32_t &s, Act act, bool correct, uint32_t fresh, uint32_t &rec)
+        {
+            const uint32_t f = ef.y, a = act();
+            // the code of the rock this step is about — under a SAMPLE, or the one a CHECK measures — read at the entry's offset
+            // (a move's entry points at the position nibble it changes: whatever this reads there is not used)
+            const uint32_t q = __builtin_amdgcn_ubfe(s, f, 2u);
+            const bool ok = ((int32_t)f < 0) & (q != 1u);                       // SAMPLE: an uncollected rock with an id < K is underfoot (REC_ROCK)
+            // the record when no live rock is sampled: the entry's own bytes without REC_ROCK, of its two ob bits the one the
+            // reading gives (CHECK rock a - 5, rock.py:171-175, 401-407: good = its code is 2)
+            const uint32_t keep = ((q == 2u) == correct) ? 0x7FFFFE00u : 0x7FFFFD00u;
+            const uint32_t rfb = (f & keep) | a;
+            // a sampled rock's code IS its outcome: 0 -> -10 (0xF6), 2 -> +10 (0x0A), never done; the action byte is SAMPLE's
+            const uint32_t rok = 0x00F60004u - q * 0x00760000u;
+            rec = ok ? rok : rfb;
+            // the state moves by a step of -1, 0 or +1 at the entry's offset: a move's nibble, or a sampled rock's code -> 1
+            const int c = ok ? 1 - (int)q : __builtin_amdgcn_sbfe((int)f, 5u, 2u);
+            const uint32_t moved = s + ((uint32_t)c << (f & 31u));
+            s = rec >= (1u << 24) ? fresh : moved;                              // done: byte 3 of the finished record
+        }
+        // the reset-tie filter is the popcount test (fresh_words): these are the boards above RESET_NUMERIC_K rocks
+        static __device__ __forceinline__ uint32_t tie_bound(int) { return 0u; }
+        template <int N> static __device__ __forceinline__ void fresh(const uint32_t (&R)[N], const RngKey &key, uint32_t first, int K, uint32_t start, uint32_t, uint32_t (&out)[N])
+        {
+            fresh_words<N, (int)ROCK0>(R, K, start, out);
+            int fewest = __popc(R[0]);
+#pragma unroll
+            for (int e = 1; e < N; ++e) fewest = min(fewest, (int)__popc(R[e]));
+            if (fewest <= 6) fresh_ties<N, (int)ROCK0>(R, key, first, K, out);
+        }
+    };
+    using RecMem = Rec8<0u>;
+    using RecRot = Rec8<ROT_POS>;
+
+    // 16-byte entries (steps_quad_kernel, one state word), for the boards wide_ok: at most RESET_NUMERIC_K = 8 rocks and a side of
+    // at most 7 (RockSample(7,8), (7,7), (4,3), (2,1): every reference board with at most eight rocks).  A coordinate is three
     // bits, 13 actions x 128 slots x 16 bytes = 26 KB (less than RecTab's 34), and one ds_read_b128 brings {E, M, recA, recB}:
-    //   E    = what the raw sensor word compares with — a CHECK: T << 5, saturated to 0xFFFFFFE0 (rec_thr_word<true>) — else
-    //          the value a step writes, where it writes it: a move that stays inside the new coordinate in its field, a SAMPLE on
-    //          a rock with an id < K the code 1 (over a collected rock's 1 as well: the state half does not ask whether the rock
-    //          was live), everything else 0;
+    //   E    = what the raw sensor word compares with — a CHECK: T << 5, saturated to 0xFFFFFFE0 (thr_word) — else the value a
+    //          step writes, where it writes it: a move that stays inside the new coordinate in its field, a SAMPLE on a rock
+    //          with an id < K the code 1 (over a collected rock's 1 as well: the state half does not ask whether the rock was
+    //          live), everything else 0;
     //   M    = the field E is inserted into — the moved coordinate's three bits, the sampled rock's two, else 0 (CHECKs too):
     //          s' = (E & M) | (s & ~M), one v_bfi_b32 — plus, in bits 0-4, the bit offset of the rock the step is about (under
-    //          a SAMPLE, or the one a CHECK measures; 0 for a move), which v_bfe_u32 reads as it is, and in bit 31 (WIDE_ROCK)
+    //          a SAMPLE, or the one a CHECK measures; 0 for a move), which v_bfe_u32 reads as it is, and in bit 31 (REC_ROCK)
     //          "a rock with an id < K lies under this SAMPLE", one signed compare;
     //   recA = the finished record (action byte, ob, reward byte, done bit) when no live rock is sampled and the reading matches
     //          the rock (ob 2 on a CHECK), recB the same when it does not (ob 1); off a CHECK the two are equal.
-    // The state word in registers: bit 31 zero, y at bits 28-30, x at 25-27, rock j's code at bit INS_ROCK0 + 2 j = 5 + 2 j (the
+    // The state word in registers: bit 31 zero, y at bits 28-30, x at 25-27, rock j's code at bit ROCK0 + 2 j = 5 + 2 j (the
     // last of eight ends at bit 20), bits 21-24 and 0-4 zero.  The bits of M that are no field — 0-4 and 31 — lie over zeros of
     // both s and E (E of a CHECK has M's fields empty, E of the others is a value inside a real field), so the insert keeps them
-    // zero; the entry's byte address a << 11 | y << 7 | x << 4 is one v_alignbit_b32(a, s, 21) with nothing to mask.  Memory
-    // keeps x | y << 4 | codes << 8 (wide_from_mem after the launch's load, wide_to_mem before its store; a coordinate above 7
-    // is no state of these boards: its fourth bit is dropped, every read stays inside the table).
+    // zero; the entry's byte address a << 11 | y << 7 | x << 4 is one v_alignbit_b32(a, s, 21) with nothing to mask.  A
+    // coordinate above 7 is no state of these boards: from_mem drops its fourth bit, every read stays inside the table.
     // Against a non-CHECK entry the tie filter H - E < TIE_SPAN passes 32 values of H (2^-27 per lane-step), its outcome unused;
-    // the slot rec_sensor_exact_wide derives from a move's offset 0 is 13: below 16.
-    static constexpr int WIDE_ACTIONS = 5 + RESET_NUMERIC_K, WIDE_SLOTS = 128;
-    static constexpr int WIDE_SIDE = 7;                      // the launcher sends larger boards to steps_quad_popc_kernel
-    static constexpr uint32_t WIDE_X = 25u, WIDE_Y = 28u, WIDE_ROCK = 1u << 31;
-    struct RecTabWide { u32x4 e[WIDE_ACTIONS][WIDE_SLOTS]; };
-    static __device__ __forceinline__ uint32_t wide_from_mem(uint32_t m)
-    {
-        return ((m & 7u) << WIDE_X) | ((m & 0x70u) << (WIDE_Y - 4u)) | ((m >> (8u - INS_ROCK0)) & (0xFFFFu << INS_ROCK0));
-    }
-    static __device__ __forceinline__ uint32_t wide_to_mem(uint32_t s)
-    {
-        return ((s >> WIDE_X) & 7u) | ((s >> (WIDE_Y - 4u)) & 0x70u) | ((s & (0xFFFFu << INS_ROCK0)) << (8u - INS_ROCK0));
-    }
-    // the start cell (x | y << 4) where this layout has the position: what fresh_states<., true, true, true> ors in
-    static __device__ __forceinline__ uint32_t wide_start(uint32_t start) { return wide_from_mem(start & 0xFFu); }
-    // one thread per slot = x | y << 3, slot < WIDE_SLOTS (slots off the board are never read)
-    static __device__ __forceinline__ void build_rec_tab_wide(RecTabWide &tab, const Shared &sh, const Params &p, int slot)
-    {
-        static_assert(W == 1, "the wide entries are the one-state-word loops'");
-        const uint32_t x = (uint32_t)slot & 7u, y = ((uint32_t)slot >> 3) & 15u, size = (uint32_t)p.size, K = (uint32_t)p.num_rocks;
-        const int id = sh.grid[x * 16 + y];
-        const uint32_t penalty = STOCH ? 0u : (0x9Cu << 16) | (1u << 24);     // -100 and done (StochasticRock: nothing, rock.py:432, 503)
-        for (int a = 0; a < 5 + (int)K && a < WIDE_ACTIONS; ++a) {
-            uint32_t E = 0u, M = 0u, recA = (uint32_t)a, recB;
-            if (a < 4) {
-                const uint32_t nx = x + (uint32_t)((a == 1) - (a == 3)), ny = y + (uint32_t)((a == 0) - (a == 2));
-                const uint32_t off = (a & 1) ? WIDE_X : WIDE_Y;
-                if (max(nx, ny) < size) { E = ((a & 1) ? nx : ny) << off; M = 7u << off; }
-                else recA |= a == 1 ? (0x0Au << 16) | (1u << 24) : penalty;      // the east exit: +10 and done
-                recB = recA;
-            } else if (a == 4) {
-                const uint32_t off = INS_ROCK0 + 2u * (uint32_t)id;
-                if ((uint32_t)id < K) { E = 1u << off; M = (3u << off) | off | WIDE_ROCK; }
-                recA |= penalty;
-                recB = recA;
-            } else {
-                E = rec_thr_word<true>(sh.thr[__builtin_amdgcn_sad_u8(x | (y << 8), sh.rpos[a - 5], 0u) & 31u].x);
-                M = INS_ROCK0 + 2u * (uint32_t)(a - 5);
-                recB = recA | (1u << 8);
-                recA |= 2u << 8;
+    // the slot `exact` derives from a move's offset 0 is 13: below 16.
+    static constexpr int WIDE_SIDE = 7;
+    // which one-word form a board takes in the quad loops: RecWide (steps_quad_kernel), else RecRot (steps_quad_popc_kernel)
+    static __host__ __device__ __forceinline__ bool wide_ok(const Params &p) { return p.num_rocks <= RESET_NUMERIC_K && p.size <= WIDE_SIDE; }
+    struct RecWide {
+        static_assert(W == 1, "one state word");
+        static constexpr int ACTIONS = 5 + RESET_NUMERIC_K, SLOTS = 128;
+        static constexpr uint32_t X0 = 25u, Y0 = 28u, ROCK0 = 5u;
+        struct Tab { u32x4 e[ACTIONS][SLOTS]; };
+        using Entry = u32x4;
+        static __device__ __forceinline__ uint32_t from_mem(uint32_t m) { return ((m & 7u) << X0) | ((m & 0x70u) << (Y0 - 4u)) | ((m >> (8u - ROCK0)) & (0xFFFFu << ROCK0)); }
+        static __device__ __forceinline__ uint32_t to_mem(uint32_t s) { return ((s >> X0) & 7u) | ((s >> (Y0 - 4u)) & 0x70u) | ((s & (0xFFFFu << ROCK0)) << (8u - ROCK0)); }
+        // the start cell (x | y << 4) where this layout has the position: what `fresh` ors the codes onto
+        static __device__ __forceinline__ uint32_t start_word(uint32_t start) { return from_mem(start & 0xFFu); }
+        // first word of a CHECK's entry from the threshold's high part T = thr >> 26 <= 2^27.  The saturated word keeps its low
+        // five bits clear — the mask word has the rock's bit offset there, and no state bit may come from under it — and every
+        // H from 0xFFFFFFE0 up passes the filter instead: `exact` finds (H >> 5) < 2^27 = T, correct, as it must be.
+        static __device__ __forceinline__ uint32_t thr_word(uint32_t T) { return T >= (1u << 27) ? 0xFFFFFFE0u : T << 5; }
+        // one thread per slot = x | y << 3 (slots off the board are never read): the threads that `builds` names
+        static __device__ __forceinline__ bool builds(uint32_t tid) { return tid < (unsigned)SLOTS; }
+        static __device__ __forceinline__ void build(Tab &tab, const Shared &sh, const Params &p, int slot)
+        {
+            const uint32_t x = (uint32_t)slot & 7u, y = ((uint32_t)slot >> 3) & 15u, size = (uint32_t)p.size, K = (uint32_t)p.num_rocks;
+            const int id = sh.grid[x * 16 + y];
+            const uint32_t penalty = STOCH ? 0u : (0x9Cu << 16) | (1u << 24);     // -100 and done (StochasticRock: nothing, rock.py:432, 503)
+            for (int a = 0; a < 5 + (int)K && a < ACTIONS; ++a) {
+                uint32_t E = 0u, M = 0u, recA = (uint32_t)a, recB;
+                if (a < 4) {
+                    const uint32_t nx = x + (uint32_t)((a == 1) - (a == 3)), ny = y + (uint32_t)((a == 0) - (a == 2));
+                    const uint32_t off = (a & 1) ? X0 : Y0;
+                    if (max(nx, ny) < size) { E = ((a & 1) ? nx : ny) << off; M = 7u << off; }
+                    else recA |= a == 1 ? (0x0Au << 16) | (1u << 24) : penalty;      // the east exit: +10 and done
+                    recB = recA;
+                } else if (a == 4) {
+                    const uint32_t off = ROCK0 + 2u * (uint32_t)id;
+                    if ((uint32_t)id < K) { E = 1u << off; M = (3u << off) | off | REC_ROCK; }
+                    recA |= penalty;
+                    recB = recA;
+                } else {
+                    E = thr_word(sh.thr[__builtin_amdgcn_sad_u8(x | (y << 8), sh.rpos[a - 5], 0u) & 31u].x);
+                    M = ROCK0 + 2u * (uint32_t)(a - 5);
+                    recB = recA | (1u << 8);
+                    recA |= 2u << 8;
+                }
+                u32x4 e = {E, M, recA, recB};
+                tab.e[a][slot] = e;
             }
-            u32x4 e = {E, M, recA, recB};
-            tab.e[a][slot] = e;
         }
-    }
-    static __device__ __forceinline__ u32x4 rec_lookup_wide(const RecTabWide &tab, uint32_t s, uint32_t a)
-    {
-        const uint32_t off = __builtin_amdgcn_alignbit(a, s, WIDE_X - 4u);
-        return *reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(&tab.e[0][0]) + off);
-    }
-    // rec_sensor_exact for this layout: the position from the word's top, the rock slot from the mask word's offset
-    template <class LowWord>
-    static __device__ __forceinline__ bool rec_sensor_exact_wide(const Shared &sh, uint32_t s, uint32_t M, uint32_t H, LowWord lo)
-    {
-        const uint32_t r = (((M & 31u) - INS_ROCK0) >> 1) & 15u;
-        return sensor_exact_at(sh, ((s >> WIDE_X) & 7u) | (((s >> WIDE_Y) & 7u) << 8), r, H, lo);
-    }
-    static __device__ __forceinline__ void rec_finish_wide(const u32x4 e, uint32_t &s, bool correct, uint32_t fresh, uint32_t &rec)
-    {
-        const uint32_t M = e.y;
-        // the code of the rock this step is about, read at the mask word's offset (a move's 0: whatever this reads is not used)
-        const uint32_t q = __builtin_amdgcn_ubfe(s, M, 2u);
-        const bool ok = ((int32_t)M < 0) & (q != 1u);                       // SAMPLE: an uncollected rock with an id < K is underfoot
-        // the record when no live rock is sampled, ready-made: the reading gives the rock's state or it does not (CHECK rock
-        // a - 5, rock.py:171-175, 401-407: good = its code is 2)
-        const uint32_t rfb = ((q != 2u) != correct) ? e.z : e.w;
-        // a sampled rock's code IS its outcome: 0 -> -10 (0xF6), 2 -> +10 (0x0A), never done; the action byte is SAMPLE's
-        const uint32_t rok = 0x00F60004u - q * 0x00760000u;
-        rec = ok ? rok : rfb;
-        // (hipcc does not form v_bfi_b32 from the C expression: two v_and_b32, a v_not_b32 and a v_or_b32)
-        uint32_t moved;
-        asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(moved) : "v"(M), "v"(e.x), "v"(s));
-        // (the record passes through a register of its own: with the state half gone from the lanes' common subexpressions the
-        // compiler otherwise builds the four records of a thread's 16-byte store as two-element vectors)
-        asm("" : "+v"(rec));
-        s = rec >= (1u << 24) ? fresh : moved;                              // done: byte 3 of the finished record
-    }
+        static __device__ __forceinline__ Entry lookup(const Tab &tab, uint32_t s, uint32_t a)
+        {
+            const uint32_t off = __builtin_amdgcn_alignbit(a, s, X0 - 4u);
+            return *reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(&tab.e[0][0]) + off);
+        }
+        // all N entries have landed: one wait (each passes as the register tuple its read filled: no copies)
+        template <int N> static __device__ __forceinline__ void settle(Entry (&e)[N])
+        {
+            if constexpr (N == 4) asm volatile("" : "+v"(e[0]), "+v"(e[1]), "+v"(e[2]), "+v"(e[3]));
+            else asm volatile("" : "+v"(e[0]), "+v"(e[1]));
+        }
+        static __device__ __forceinline__ uint32_t cmp(const Entry e) { return e.x; }
+        // the position from the word's top; the measured rock off the mask word's offset, not the action, so that a tape-driven
+        // loop's rare path does not keep a tape row it wants to load over alive
+        template <class LowWord> static __device__ __forceinline__ bool exact(const Shared &sh, uint32_t s, const Entry e, uint32_t H, LowWord lo)
+        {
+            const uint32_t r = (((e.y & 31u) - ROCK0) >> 1) & 15u;
+            return sensor_exact_at(sh, ((s >> X0) & 7u) | (((s >> Y0) & 7u) << 8), r, H, lo);
+        }
+        template <class Act> static __device__ __forceinline__ void finish(const Entry e, uint32_t &s, Act, bool correct, uint32_t fresh, uint32_t &rec)
+        {
+            const uint32_t M = e.y;
+            // the code of the rock this step is about, read at the mask word's offset (a move's 0: whatever this reads is not used)
+            const uint32_t q = __builtin_amdgcn_ubfe(s, M, 2u);
+            const bool ok = ((int32_t)M < 0) & (q != 1u);                       // SAMPLE: an uncollected rock with an id < K is underfoot
+            // the record when no live rock is sampled, ready-made: the reading gives the rock's state or it does not (CHECK rock
+            // a - 5, rock.py:171-175, 401-407: good = its code is 2)
+            const uint32_t rfb = ((q != 2u) != correct) ? e.z : e.w;
+            // a sampled rock's code IS its outcome: 0 -> -10 (0xF6), 2 -> +10 (0x0A), never done; the action byte is SAMPLE's
+            const uint32_t rok = 0x00F60004u - q * 0x00760000u;
+            rec = ok ? rok : rfb;
+            // (hipcc does not form v_bfi_b32 from the C expression: two v_and_b32, a v_not_b32 and a v_or_b32)
+            uint32_t moved;
+            asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(moved) : "v"(M), "v"(e.x), "v"(s));
+            // (the record passes through a register of its own: with the state half gone from the lanes' common subexpressions the
+            // compiler otherwise builds the four records of a thread's 16-byte store as two-element vectors)
+            asm("" : "+v"(rec));
+            s = rec >= (1u << 24) ? fresh : moved;                              // done: byte 3 of the finished record
+        }
+        // the reset-tie filter is numeric (fresh_words): its bound 2^(2 K + 5), in a scalar register
+        static __device__ __forceinline__ uint32_t tie_bound(int K) { uint32_t b = 1u << (2 * min(K, RESET_NUMERIC_K) + 5); asm volatile("" : "+s"(b)); return b; }
+        // (the word shifted up by ROCK0, then one v_and_or_b32)
+        template <int N> static __device__ __forceinline__ void fresh(const uint32_t (&R)[N], const RngKey &key, uint32_t first, int K, uint32_t start, uint32_t bound, uint32_t (&out)[N])
+        {
+            fresh_words<N, (int)ROCK0>(R, K, start, out);
+            uint32_t least = R[0];
+#pragma unroll
+            for (int e = 1; e < N; ++e) least = min(least, R[e]);
+            if (least < bound) fresh_ties<N, (int)ROCK0>(R, key, first, K, out);
+        }
+    };
+    // rock.py:123-194 for one lane: s -> s' (the fresh episode `fresh` if the step ends this one), rec = the step's record.
+    // H: the lane's sensor high word; `lo` yields its low word (a tie, 2^-27 per CHECK).  One state word: the two halves of
+    // RecMem back to back.  Two state words (K > 12): the rock codes run on into the upper word (rock j at bits 8 + 2 j), a code
+    // never straddles the words, and the word a SAMPLE or a CHECK reads is a select on bit 5 of its bit offset.
     template <class LowWord>
     static __device__ __forceinline__ void step_rec(const Shared &sh, const RecTab &tab, S &s, uint32_t a, uint32_t H, S fresh,
                                                     uint32_t &rec, LowWord lo)
     {
         const uint32_t s_lo = (uint32_t)s, s_hi = W == 2 ? (uint32_t)((uint64_t)s >> 32) : 0u;
         if constexpr (W == 1) {
-            const uint2 ef = rec_lookup(tab, s_lo, a);
-            bool correct = H < ef.x;                                            // the raw word against the entry itself
-            if (H - ef.x < TIE_SPAN) correct = rec_sensor_exact(sh, s_lo, ef.y, H, lo);   // 2^-27 per CHECK
+            const auto ef = RecMem::lookup(tab, s_lo, a);
+            bool correct = H < RecMem::cmp(ef);                                 // the raw word against the entry itself
+            if (H - RecMem::cmp(ef) < TIE_SPAN) correct = RecMem::exact(sh, s_lo, ef, H, lo);   // 2^-27 per CHECK
             uint32_t sn = s_lo;
-            rec_finish(ef, sn, a, correct, (uint32_t)fresh, rec);
+            RecMem::finish(ef, sn, [&]() { return a; }, correct, (uint32_t)fresh, rec);
             s = (S)sn;
         } else {
             const uint32_t e = tab.e[a][s_lo & 0xFFu];

@@ -370,7 +370,7 @@ static int launch_episodes_l(const typename Env::Params &p, uint32_t *state, uin
     const RngKey key = make_key(seed, t);
     if constexpr (rock_quad_of<Env>::value) {
         bool quad_ok = n % (4 * BLOCK) == 0 && n >= (Env::STOCHASTIC ? QUAD_MIN_STOCHROCK : QUAD_MIN_ROCK) && k >= 16 &&
-                       p.num_rocks + 5 <= Env::TAB_ACTIONS && (reinterpret_cast<uintptr_t>(state) & 15u) == 0 &&
+                       Env::tab_ok(p) && (reinterpret_cast<uintptr_t>(state) & 15u) == 0 &&
                        (reinterpret_cast<uintptr_t>(done) & 3u) == 0 && rec % 4 == 0;
         if (L::ID == POMDP_LAYOUT_PACKED) quad_ok = quad_ok && (reinterpret_cast<uintptr_t>(out0) & 15u) == 0;
         if (L::ID == POMDP_LAYOUT_NARROW) quad_ok = quad_ok && (reinterpret_cast<uintptr_t>(out0) & 3u) == 0;

@@ -361,19 +361,16 @@ __global__ __launch_bounds__(BLOCK) void steps_kernel(uint32_t *__restrict__ sta
 // One state word (round 13): the lane step runs in two phases — the table reads of all of the thread's lanes, ONE wait, every
 // compare, ONE exec-masked branch for the lanes whose sensor draw the high word leaves undecided (with the reset-tie filter:
 // two per step, where each lane had its own read -> wait -> compare -> branch), then the records — on a state word kept
-// rotated in registers (rock.hip.h: RecTab), and packed records leave through a scalar row base (traj_out.hip.h: PackedRowOut).
-// With at most eight rocks (round 15, INS) the word carries the codes five bits up and a step changes it by one masked insert
-// of the table entry's first word; since round 16 the entry is 16 bytes (rock.hip.h: RecTabWide, one ds_read_b128) and brings
-// the insert's mask and both finished records along: no v_bfm_b32, no v_and_or_b32 per lane.
+// in a layout of its own in registers, and packed records leave through a scalar row base (traj_out.hip.h: PackedRowOut).  Which
+// layout, and which table entry with it, is Form's business alone (rock.hip.h: RecWide — 16-byte entries, the state changed by
+// one masked insert, boards RockEnv::wide_ok — or RecRot; two state words: RecMem for its table, the step is RockEnv::step_rec).
 // LPT = 2 (round 6): HALF a quad per thread, for the shards that leave the quad loop two waves per SIMD or fewer (2^19 lanes
 // — half of a 2^20-lane batch — ran the pooled two-lanes-per-thread steps_kernel at 0.46 of its issue floor).  The quad's
 // STEP block (and StochasticRock's gate block) is time-shared by the quad's two threads exactly like the policy's block
 // (pair_shared: thread e computes the block of step s + e at every even s, two DPP moves swap the halves): one block of each
 // stream per thread per two steps — as many per lane-step as with a quad per thread — and twice the waves.  4-byte sinks and
 // the returns sink (PairOut).
-// NUMERIC (one state word): which filter sends a thread to look for reset ties, RockEnv::fresh_states — by number up to
-// RockEnv::RESET_NUMERIC_K rocks (steps_quad_kernel), by popcount above (steps_quad_popc_kernel); the launcher picks by the board.
-template <class Env, class L, class Pol, int LPT, bool NUMERIC>
+template <class Env, class L, class Pol, int LPT, class Form>
 __device__ __forceinline__ void steps_quad_body(uint32_t *__restrict__ state, int32_t *__restrict__ action,
                                                 int32_t *__restrict__ ob, int32_t *__restrict__ reward,
                                                 uint8_t *__restrict__ done, int64_t n, RngKey key0, uint32_t lane0,
@@ -382,21 +379,9 @@ __device__ __forceinline__ void steps_quad_body(uint32_t *__restrict__ state, in
 {
     static_assert(LPT == 4 || LPT == 2, "a quad or half a quad per thread");
     constexpr int W = Env::WORDS;
-    // one state word: the loop keeps it rotated right by 8 — rock codes from bit 0, the position byte on top — so that a fresh
-    // episode is one v_and_or_b32 of the lane's sensor word (RockEnv::build_rec_tab<true>); memory keeps its layout
-    constexpr bool ROT = W == 1;
-    // ... and, with the numeric filter's boards (at most RockEnv::RESET_NUMERIC_K rocks, a side of at most 7), the codes five bits
-    // up, clear of the word's low bits, under two three-bit coordinates: the state changes by one masked insert from a 16-byte
-    // table entry (RockEnv::build_rec_tab_wide)
-    constexpr bool INS = ROT && NUMERIC;
     using S = typename Env::S;
     __shared__ typename Env::Shared sh;
-    // the lane step yields the lane's packed record straight from RecTab (one state word: RockEnv::rec_lookup / rec_finish, 17
-    // vector instructions per lane-step and one for the fresh episode it may need — INS: rec_lookup_wide / rec_finish_wide, 12
-    // and two; two words: RockEnv::step_rec)
-    using Tab = typename std::conditional<INS, typename Env::RecTabWide, typename Env::RecTab>::type;
-    using Entry = typename std::conditional<INS, u32x4, uint2>::type;
-    __shared__ Tab tab;
+    __shared__ typename Form::Tab tab;                       // the lane step yields the lane's packed record straight from it
     const uint32_t n_act = (uint32_t)Env::n_actions(p);
     // a quad per thread on a tape: the loop unrolled by two, the tape read two steps ahead (TapeQuadAhead)
     constexpr bool AHEAD2 = Pol::TAPE && LPT == 4;
@@ -425,32 +410,27 @@ __device__ __forceinline__ void steps_quad_body(uint32_t *__restrict__ state, in
         cx.first(gen_first, a_cur);
 #pragma unroll
         for (int j = 0; j < LPT; ++j) {
-            if constexpr (INS) st[j].s = Env::wide_from_mem(s_lo[j]);
-            else if constexpr (ROT) st[j].s = __builtin_amdgcn_alignbit(s_lo[j], s_lo[j], 8u);
+            if constexpr (W == 1) st[j].s = Form::from_mem(s_lo[j]);
             else st[j].s = (S)((uint64_t)s_lo[j] | ((uint64_t)s_hi[j] << 32));
         }
     }
     Env::stage(sh, p, (int)threadIdx.x);
     __syncthreads();
-    if constexpr (INS) {
-        if (threadIdx.x < (unsigned)Env::WIDE_SLOTS) Env::build_rec_tab_wide(tab, sh, p, (int)threadIdx.x);
-    } else Env::template build_rec_tab<ROT>(tab, sh, p, (int)threadIdx.x);
+    if constexpr (W == 1) { if (Form::builds(threadIdx.x)) Form::build(tab, sh, p, (int)threadIdx.x); }
+    else Env::build_rec_tab(tab, sh, p, (int)threadIdx.x);
     __syncthreads();
     const int K = p.num_rocks;
     const uint32_t start = (uint32_t)p.start_x | ((uint32_t)p.start_y << 4);
-    // ... where the rotated layout has it, in a vector register: (H & codes) | start is then one v_and_or_b32 (two scalar
-    // operands do not fit one instruction)
-    uint32_t start_rot = start << (ROT ? Env::ROT_POS : 0u);
-    if constexpr (INS) start_rot = Env::wide_start(start);
-    if constexpr (ROT) asm volatile("" : "+v"(start_rot));
+    // ... where the form's layout has it, in a vector register: (H & codes) | start is then one v_and_or_b32 (two scalar
+    // operands do not fit one instruction); and the bound of its reset-tie filter
+    uint32_t start_rot = start, tie_bound = 0;
+    if constexpr (W == 1) { start_rot = Form::start_word(start); asm volatile("" : "+v"(start_rot)); }
     const LoopPrio prio(k_steps);
     constexpr uint32_t SENSOR_BLOCK = Env::SENSOR_BLOCK;
     // a quad per thread: the quad's STEP blocks have counter words 0 and 3 fixed for the launch (philox4x32_10_fixed)
     const PhiloxFixed sensor_fx = philox_fixed(glane0 >> 2, ((uint32_t)POMDP_STREAM_STEP << 24) | SENSOR_BLOCK, key0.k1);
     const PhiloxFixed gate_fx = philox_fixed(glane0 >> 2, (uint32_t)POMDP_STREAM_STEP << 24, key0.k1);
-    // the bound of the numeric reset-tie filter, RockEnv::fresh_states, in a scalar register
-    uint32_t tie_bound = 0;
-    if constexpr (ROT && NUMERIC) { tie_bound = Env::reset_tie_bound(K); asm volatile("" : "+s"(tie_bound)); }
+    if constexpr (W == 1) tie_bound = Form::tie_bound(K);
     auto step_body = [&](const int s, const auto par_) __attribute__((always_inline)) {
         constexpr int PAR = decltype(par_)::value;           // AHEAD2: s & 1
         const RngKey key = cx.key(key0, s);
@@ -492,52 +472,33 @@ __device__ __forceinline__ void steps_quad_body(uint32_t *__restrict__ state, in
         auto low_word = [&](int j) __attribute__((always_inline)) {
             return Env::elem(Env::quad_block(rare_key(key), glane0 + (uint32_t)j, SENSOR_BLOCK + 1u), e0 + (uint32_t)j);
         };
-        if constexpr (ROT) {
+        if constexpr (W == 1) {
             // the lane step in two phases: every table read of the thread first — one wait for all of them — then ONE branch
             // for the lanes whose sensor draw the high word may leave undecided (H - e < TIE_SPAN; 2^-27 per CHECK), then every
             // compare and the records
             uint32_t fresh[LPT], sn[LPT];
-            Entry ef[LPT];
-            Env::template fresh_states<LPT, true, NUMERIC, INS>(H, key, glane0, K, start_rot, tie_bound, fresh);
+            typename Form::Entry ef[LPT];
+            Form::template fresh<LPT>(H, key, glane0, K, start_rot, tie_bound, fresh);
 #pragma unroll
-            for (int j = 0; j < LPT; ++j) {
-                if constexpr (INS) ef[j] = Env::rec_lookup_wide(tab, st[j].s, valid[j] ? a_taken[j] : 0u);
-                else ef[j] = Env::template rec_lookup<true>(tab, st[j].s, valid[j] ? a_taken[j] : 0u);
-            }
-            // all of them have landed: one wait (each entry passes as the register tuple its read filled: no copies)
-            if constexpr (INS) {
-                if constexpr (LPT == 4) asm volatile("" : "+v"(ef[0]), "+v"(ef[1]), "+v"(ef[2]), "+v"(ef[3]));
-                else asm volatile("" : "+v"(ef[0]), "+v"(ef[1]));
-            } else {
-                uint64_t w[LPT];
-#pragma unroll
-                for (int j = 0; j < LPT; ++j) w[j] = (uint64_t)ef[j].x | ((uint64_t)ef[j].y << 32);
-                if constexpr (LPT == 4) asm volatile("" : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]));
-                else asm volatile("" : "+v"(w[0]), "+v"(w[1]));
-#pragma unroll
-                for (int j = 0; j < LPT; ++j) ef[j] = make_uint2((uint32_t)w[j], (uint32_t)(w[j] >> 32));
-            }
+            for (int j = 0; j < LPT; ++j) ef[j] = Form::lookup(tab, st[j].s, valid[j] ? a_taken[j] : 0u);
+            Form::template settle<LPT>(ef);                                 // all of them have landed: one wait
             // H - e with its borrow: the borrow IS `correct` = H < e, the difference feeds the filter (one v_sub_co_u32 per lane)
             uint32_t near[LPT];
             bool correct[LPT];
 #pragma unroll
-            for (int j = 0; j < LPT; ++j) correct[j] = __builtin_sub_overflow(H[j], ef[j].x, &near[j]);
+            for (int j = 0; j < LPT; ++j) correct[j] = __builtin_sub_overflow(H[j], Form::cmp(ef[j]), &near[j]);
             uint32_t nearest = near[0];
 #pragma unroll
             for (int j = 1; j < LPT; ++j) nearest = min(nearest, near[j]);
             if (nearest < Env::TIE_SPAN) {
 #pragma unroll
                 for (int j = 0; j < LPT; ++j)
-                    if (near[j] < Env::TIE_SPAN) {
-                        if constexpr (INS) correct[j] = Env::rec_sensor_exact_wide(sh, st[j].s, ef[j].y, H[j], [&]() { return low_word(j); });
-                        else correct[j] = Env::template rec_sensor_exact<true>(sh, st[j].s, ef[j].y, H[j], [&]() { return low_word(j); });
-                    }
+                    if (near[j] < Env::TIE_SPAN) correct[j] = Form::exact(sh, st[j].s, ef[j], H[j], [&]() { return low_word(j); });
             }
 #pragma unroll
             for (int j = 0; j < LPT; ++j) {
                 sn[j] = st[j].s;
-                if constexpr (INS) Env::rec_finish_wide(ef[j], sn[j], correct[j], fresh[j], rec[j]);
-                else Env::rec_finish(ef[j], sn[j], valid[j] ? a_taken[j] : 0u, correct[j], fresh[j], rec[j]);
+                Form::finish(ef[j], sn[j], [&]() { return valid[j] ? a_taken[j] : 0u; }, correct[j], fresh[j], rec[j]);
             }
 #pragma unroll
             for (int j = 0; j < LPT; ++j) {
@@ -593,14 +554,13 @@ __device__ __forceinline__ void steps_quad_body(uint32_t *__restrict__ state, in
     } else {
         POMDP_FUSED_STEP_LOOP(prio, s) step_body(s, std::integral_constant<int, 0>{});
     }
-    // the state is the loop's carry: it reaches memory once (one state word: rotated back into its memory layout)
+    // the state is the loop's carry: it reaches memory once (one state word: back in its memory layout)
     cx.finish(k_steps);
     uint32_t w_lo[LPT];
 #pragma unroll
     for (int j = 0; j < LPT; ++j) {
-        const uint32_t sj = (uint32_t)st[j].s;
-        if constexpr (INS) w_lo[j] = Env::wide_to_mem(sj);
-        else w_lo[j] = ROT ? __builtin_amdgcn_alignbit(sj, sj, 24u) : sj;
+        w_lo[j] = (uint32_t)st[j].s;
+        if constexpr (W == 1) w_lo[j] = Form::to_mem(w_lo[j]);
     }
     if constexpr (LPT == 4) {
         st_stream4(state + l0, w_lo[0], w_lo[1], w_lo[2], w_lo[3]);
@@ -619,9 +579,10 @@ __global__ __launch_bounds__(BLOCK) void steps_quad_kernel(uint32_t *__restrict_
                                                            RngKey akey0, int k_steps, int64_t rec, int gen_first,
                                                            const typename Env::Params p, TapeRef tape)
 {
-    steps_quad_body<Env, L, Pol, LPT, Env::WORDS == 1>(state, action, ob, reward, done, n, key0, lane0, akey0, k_steps, rec, gen_first, p, tape);
+    using Form = typename std::conditional<Env::WORDS == 1, typename Env::RecWide, typename Env::RecMem>::type;
+    steps_quad_body<Env, L, Pol, LPT, Form>(state, action, ob, reward, done, n, key0, lane0, akey0, k_steps, rec, gen_first, p, tape);
 }
-// ... for the one-state-word boards with more than RockEnv::RESET_NUMERIC_K rocks
+// ... for the one-state-word boards that are not RockEnv::wide_ok
 template <class Env, class L = Columns, class Pol = SyntheticQuad, int LPT = 4>
 __global__ __launch_bounds__(BLOCK) void steps_quad_popc_kernel(uint32_t *__restrict__ state, int32_t *__restrict__ action,
                                                                 int32_t *__restrict__ ob, int32_t *__restrict__ reward,
@@ -629,8 +590,8 @@ __global__ __launch_bounds__(BLOCK) void steps_quad_popc_kernel(uint32_t *__rest
                                                                 RngKey akey0, int k_steps, int64_t rec, int gen_first,
                                                                 const typename Env::Params p, TapeRef tape)
 {
-    static_assert(Env::WORDS == 1, "two state words take reset_codes4");
-    steps_quad_body<Env, L, Pol, LPT, false>(state, action, ob, reward, done, n, key0, lane0, akey0, k_steps, rec, gen_first, p, tape);
+    static_assert(Env::WORDS == 1, "two state words take steps_quad_kernel");
+    steps_quad_body<Env, L, Pol, LPT, typename Env::RecRot>(state, action, ob, reward, done, n, key0, lane0, akey0, k_steps, rec, gen_first, p, tape);
 }
 
 // Tag (one opponent) with a quad per thread: the policy's ACTION block is the thread's own, and so is the quad's STEP block —
@@ -1410,24 +1371,22 @@ static int launch_steps_fused_l(const typename Env::Params &p, uint32_t *state, 
         if constexpr (pair_sink<L>::value && !RETS) {
             // half a quad per thread where a quad per thread would leave a SIMD two waves or fewer (the shards of a 2^20-lane batch)
             if (quad_ok && n >= (Env::STOCHASTIC ? STOCHROCK_PAIR_MIN_LANES : ROCK_PAIR_MIN_LANES) &&
-                n <= (Env::STOCHASTIC ? STOCHROCK_PAIR_MAX_LANES : ROCK_PAIR_MAX_LANES) && k >= 16 && p.num_rocks + 5 <= Env::TAB_ACTIONS) {
+                n <= (Env::STOCHASTIC ? STOCHROCK_PAIR_MAX_LANES : ROCK_PAIR_MAX_LANES) && k >= 16 && Env::tab_ok(p)) {
                 char pname[40];
                 snprintf(pname, sizeof pname, "%s, 2", lname);
                 note_fused("steps_quad_kernel", Env::NAME, pname);
-                // (one state word: the reset-tie filter by number or by popcount, RockEnv::fresh_states — the same loop otherwise)
-                // (... and the 16-byte table entries' three-bit coordinates want a side of at most RockEnv::WIDE_SIDE: every
-                // reference board with at most eight rocks has one)
+                // (one state word: the same loop on RockEnv::RecWide or RecRot, by the board)
                 bool popc = false;
-                if constexpr (Env::WORDS == 1) popc = p.num_rocks > Env::RESET_NUMERIC_K || p.size > Env::WIDE_SIDE;
+                if constexpr (Env::WORDS == 1) popc = !Env::wide_ok(p);
                 if constexpr (Env::WORDS == 1) { if (popc) POMDP_LAUNCH_PAIR(steps_quad_popc_kernel<Env, L); }
                 if (!popc) POMDP_LAUNCH_PAIR(steps_quad_kernel<Env, L);
                 launched = true;
             }
         }
-        if (!launched && quad_ok && n >= (Env::STOCHASTIC ? QUAD_MIN_STOCHROCK : QUAD_MIN_ROCK) && k >= 16 && p.num_rocks + 5 <= Env::TAB_ACTIONS) {
+        if (!launched && quad_ok && n >= (Env::STOCHASTIC ? QUAD_MIN_STOCHROCK : QUAD_MIN_ROCK) && k >= 16 && Env::tab_ok(p)) {
             note_fused("steps_quad_kernel", Env::NAME, lname);
             bool popc = false;
-            if constexpr (Env::WORDS == 1) popc = p.num_rocks > Env::RESET_NUMERIC_K || p.size > Env::WIDE_SIDE;
+            if constexpr (Env::WORDS == 1) popc = !Env::wide_ok(p);
             if constexpr (Env::WORDS == 1) { if (popc) POMDP_LAUNCH_QUAD(steps_quad_popc_kernel<Env, L); }
             if (!popc) POMDP_LAUNCH_QUAD(steps_quad_kernel<Env, L);
             launched = true;
@@ -1440,7 +1399,7 @@ static int launch_steps_fused_l(const typename Env::Params &p, uint32_t *state, 
                 // by four, RockSample's table-driven step) with the tape read four rows ahead
                 if (!launched && (flags & POMDP_AUTO_RESET) && n % BLOCK == 0) {
                     bool tab = false;
-                    if constexpr (quad_tab<Env>::value && Env::QUAD_SENSOR) tab = k >= 16 && p.num_rocks + 5 <= Env::TAB_ACTIONS;
+                    if constexpr (quad_tab<Env>::value && Env::QUAD_SENSOR) tab = k >= 16 && Env::tab_ok(p);
                     snprintf(variant, sizeof variant, ", 1, true, %s%s", tab ? "true" : "false", lname);
                     note_fused("steps_kernel", Env::NAME, variant);
                     if constexpr (quad_tab<Env>::value && Env::QUAD_SENSOR) {
@@ -1476,7 +1435,7 @@ static int launch_steps_fused_l(const typename Env::Params &p, uint32_t *state, 
     }
     if constexpr (quad_tab<Env>::value && Env::QUAD_SENSOR) {
         // RockSample's small shards, one lane per thread: the table-driven lane step from 16 steps per launch on
-        if (!launched && simple && k >= 16 && p.num_rocks + 5 <= Env::TAB_ACTIONS) {
+        if (!launched && simple && k >= 16 && Env::tab_ok(p)) {
             snprintf(variant, sizeof variant, ", 1, true, true%s", lname);
             note_fused("steps_kernel", Env::NAME, variant);
             hipLaunchKernelGGL((steps_kernel<Env, 1, true, true, L>), grid, dim3(BLOCK), 0, (hipStream_t)stream, state, action, ob, reward,

@@ -1,5 +1,5 @@
 """RockSample's quad and half-quad loops (steps_quad_kernel) since the state changes by one masked insert of the table entry's
-first word (rock.hip.h: build_rec_tab<true, true>, boards with at most eight rocks): scripted tapes against the C oracle.
+first word (rock.hip.h: RecWide::build, boards with at most eight rocks): scripted tapes against the C oracle.
 
 The loop keeps the state word in a layout of its own — position byte on top, rock j's code at bit 5 + 2 j — and converts when
 the launch loads and stores it; a move inserts the new nibble, a SAMPLE on a rock the code 1 (over a collected rock's 1 too).

@@ -1,4 +1,4 @@
-"""RockSample's quad and half-quad loops (steps_quad_kernel) on 16-byte table entries (rock.hip.h: RecTabWide): the launches a
+"""RockSample's quad and half-quad loops (steps_quad_kernel) on 16-byte table entries (rock.hip.h: RecWide): the launches a
 tape does not reach, and the tape's invalid actions.
 
 With the wide entries the record's action byte comes out of the table — the action only addresses the entry — and the state

@@ -4,11 +4,11 @@ host only.
 The entry's first word is what the lane's sensor high word H compares with (gym_pomdp_amd/csrc/envs/rock.hip.h): a CHECK
 stores E = T << 5 with T = thr >> 26, saturated to 0xFFFFFFFF where T = 2^27 (the always-right sensor at distance 0), every
 other entry 0xFFFFFFFF; the rock-under-a-SAMPLE flag sits in bit 31 of the second word.  `correct` = H < E on the common path;
-a lane with H - E < 32 (unsigned) recomputes the draw from the threshold itself (rec_sensor_exact).  The packing is device
+a lane with H - E < 32 (unsigned) recomputes the draw from the threshold itself (Rec8::exact).  The packing is device
 code, so it is restated here and held against the definition it replaces — (H >> 5) < T, or the low word against the
 threshold's low 26 bits when (H >> 5) == T — and against test_rock_rec_tab_host.py's restatement of the old entry.
 
-fresh_states' filter for K <= RESET_NUMERIC_K rocks is numeric: a tied rock j means rotr(w, 2 j + 2) in [2^31, 2^31 + 32), so
+fresh_words' filter for K <= RESET_NUMERIC_K rocks is numeric: a tied rock j means rotr(w, 2 j + 2) in [2^31, 2^31 + 32), so
 bit 2 j + 1 and bits 2 j + 2 .. 2 j + 6 are the only ones that may be set: w < 2^(2 K + 5)."""
 import os
 import re
@@ -33,7 +33,7 @@ def header_const(name):
 
 
 def rec_thr_word(T):
-    """RockEnv::rec_thr_word"""
+    """RockEnv::rec_thr_word (RecWide::thr_word keeps the low five bits of the saturated word clear)"""
     return M32 if T >= 1 << 27 else T << 5
 
 
@@ -44,7 +44,7 @@ def old_decision(H, L, thr):
 
 
 def new_decision(H, L, thr, E):
-    """the common compare, patched by the rare path whenever H - E < TIE_SPAN (RockEnv::rec_sensor_exact)"""
+    """the common compare, patched by the rare path whenever H - E < TIE_SPAN (RockEnv::Rec8::exact)"""
     correct = H < E
     if (H - E) & M32 < TIE_SPAN:
         kh, T = H >> 5, thr >> 26
@@ -53,7 +53,7 @@ def new_decision(H, L, thr, E):
 
 
 def rec_finish_new(f, s, a, correct, fresh):
-    """RockEnv::rec_finish with the flag in the second word -> (record, new state)"""
+    """RockEnv::Rec8::finish with the flag in the second word -> (record, new state)"""
     off = f & 31
     q = (s >> off) & 3
     ok = bool(f >> 31) and q != 1
@@ -160,7 +160,7 @@ def popc(w):
 
 
 def filter_passes(words, K, numeric_k):
-    """RockEnv::fresh_states' way into the tie branch for one thread's words (four of a quad, two of half a quad)"""
+    """RockEnv::fresh_words' way into the tie branch (the filters of RecWide::fresh / Rec8::fresh) for one thread's words (four of a quad, two of half a quad)"""
     if K <= numeric_k:
         return min(words) < 1 << (2 * K + 5)
     return min(popc(w) for w in words) <= 6

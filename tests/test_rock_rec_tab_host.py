@@ -2,7 +2,7 @@
 
 steps_quad_kernel keeps a one-word state rotated right by 8 in registers: rock j's code at bits 2 j, 2 j + 1, the position
 byte on top at bits 24-31 (RockEnv::ROT_POS in gym_pomdp_amd/csrc/envs/rock.hip.h); memory keeps x | y << 4 | codes << 8.
-The table builder is device code, so its packing (rec_f, build_rec_tab, rec_finish) is restated here for both layouts and the
+The table builder is device code, so its packing (rec_f, build_rec_tab, Rec8::finish) is restated here for both layouts and the
 two are run against each other: a step in the rotated layout must be the rotation of the step in memory layout, for every
 cell, action, rock code and reading — in particular for the last rock of a 12-rock board, whose code sits right under the
 position byte, where a carry out of `s + (c << off)` would move the agent.
@@ -38,7 +38,7 @@ def rec_f(off, c, ob_mask, oc):
 
 
 def build_rec_tab(size, rocks, rot, pos0):
-    """-> {(a, pos): (e, f)} as RockEnv<1>::build_rec_tab<rot>; the CHECK entries' thresholds left out (e = NOTHING)"""
+    """-> {(a, pos): (e, f)} as RockEnv<1>::build_rec_tab<POS0> (rot: POS0 = ROT_POS, else 0); the CHECK entries' thresholds left out (e = NOTHING)"""
     K = len(rocks)
     grid = {(x, y): j for j, (x, y) in enumerate(rocks)}
     p0, r0 = (pos0, 0) if rot else (0, 8)
@@ -64,7 +64,7 @@ def build_rec_tab(size, rocks, rot, pos0):
 
 
 def rec_finish(e, f, s, a, correct, fresh):
-    """RockEnv::rec_finish -> (record, new state)"""
+    """RockEnv::Rec8::finish -> (record, new state)"""
     off = f & 31
     q = (s >> off) & 3
     ok = bool(e >> 31) and q != 1

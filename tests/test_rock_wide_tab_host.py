@@ -1,7 +1,7 @@
 """The 16-byte table entries of RockSample's quad loop on the boards with at most eight rocks — host only.
 
-steps_quad_kernel reads one entry {E, M, recA, recB} per lane-step (gym_pomdp_amd/csrc/envs/rock.hip.h: RecTabWide,
-build_rec_tab_wide, rec_finish_wide) and keeps the state word in a layout of its own: bit 31 zero, y at bits 28-30, x at 25-27,
+steps_quad_kernel reads one entry {E, M, recA, recB} per lane-step (gym_pomdp_amd/csrc/envs/rock.hip.h: RecWide, its
+Tab, build and finish) and keeps the state word in a layout of its own: bit 31 zero, y at bits 28-30, x at 25-27,
 rock j's code at bit 5 + 2 j, everything else zero; memory keeps x | y << 4 | codes << 8.  The builder and the lane step are
 device code, so both are restated here and run against test_rock_rec_tab_host.py's restatement of the 8-byte form in memory
 layout: for every board the form serves — (7,8), (7,7), (4,3), (2,1) — every (action, cell of the board, code of the rock the
@@ -28,7 +28,7 @@ def to_mem(s):
 
 
 def build_wide(size, K, stoch=False):
-    """-> {(a, x, y): (E, M, recA, recB)} as RockEnv<1>::build_rec_tab_wide; a CHECK's E (the threshold word) left 0"""
+    """-> {(a, x, y): (E, M, recA, recB)} as RockEnv<1>::RecWide::build; a CHECK's E (the threshold word) left 0"""
     grid = {}
     for j, c in enumerate(tables.ROCK_CONFIG[size][2]):          # every listed coordinate is stamped, the last one wins
         grid[tuple(c)] = j
@@ -62,7 +62,7 @@ def build_wide(size, K, stoch=False):
 
 
 def finish_wide(entry, s, correct, fresh):
-    """RockEnv::rec_finish_wide -> (record, new state)"""
+    """RockEnv::RecWide::finish -> (record, new state)"""
     E, M, recA, recB = entry
     q = (s >> (M & 31)) & 3
     ok = bool(M >> 31) and q != 1
