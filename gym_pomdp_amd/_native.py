@@ -17,8 +17,8 @@ LIB_PATH = os.environ.get("GYM_POMDP_AMD_LIB") or INTREE_LIB_PATH
 # one object per translation unit (built in parallel), linked into one shared library
 UNITS = ["api.hip", "step_rock.hip", "step_other.hip", "fused_rock.hip", "fused_stochrock.hip", "fused_tag.hip",
          "fused_battleship.hip", "fused_misc.hip", "planner.hip", "episodes.hip",
-         "particles.hip", "planner_preferred.hip"]
-HEADERS = ["kernels_common.hip.h", "planner_common.hip.h", "traj_out.hip.h", "step_impl.hip.h", "fused_impl.hip.h", "envs.hip.h", "envs_common.hip.h", "philox.hip.h",
+         "particles.hip", "planner_preferred.hip", "heuristic_collect.hip"]
+HEADERS = ["kernels_common.hip.h", "planner_common.hip.h", "heuristic_impl.hip.h", "traj_out.hip.h", "step_impl.hip.h", "fused_impl.hip.h", "envs.hip.h", "envs_common.hip.h", "philox.hip.h",
            "envs/rock.hip.h", "envs/tag.hip.h", "envs/battleship.hip.h", "envs/tiger.hip.h", "envs/network.hip.h"]
 SOURCES = [os.path.join(_PKG, "csrc", f) for f in UNITS + HEADERS]
 HEADER = os.path.join(_REPO, "include", "pomdp_hip.h")
@@ -41,7 +41,7 @@ SYMBOLS = [
     "pomdp_network_reset", "pomdp_network_step", "pomdp_step", "pomdp_step_sync", "pomdp_reset_sync", "pomdp_stream_sync", "pomdp_synthetic_actions", "pomdp_philox_blocks",
     "pomdp_rollout_synthetic", "pomdp_collect_synthetic", "pomdp_collect", "pomdp_collect_layout", "pomdp_collect_traj", "pomdp_packed_reward", "pomdp_decode_packed", "pomdp_collect_returns", "pomdp_collect_tape", "pomdp_collect_tape_layout", "pomdp_collect_tape_returns", "pomdp_fuse_max", "pomdp_fuse_steps", "pomdp_legal_actions", "pomdp_rollout", "pomdp_plan", "pomdp_plan_reduce", "pomdp_compute_prob",
     "pomdp_rock_belief_reset", "pomdp_rock_belief_refresh", "pomdp_rock_belief_update", "pomdp_rock_select_target", "pomdp_history_clear",
-    "pomdp_history_append", "pomdp_preferred_actions", "pomdp_pick_actions", "pomdp_heuristic_steps",
+    "pomdp_history_append", "pomdp_preferred_actions", "pomdp_pick_actions", "pomdp_heuristic_steps", "pomdp_heuristic_collect",
     "pomdp_reset_where", "pomdp_finish_episodes",
     "pomdp_particle_init", "pomdp_particle_update", "pomdp_plan_particles",
     "pomdp_rollout_preferred_workspace", "pomdp_rollout_preferred", "pomdp_plan_preferred",
@@ -272,6 +272,8 @@ def lib():
     L.pomdp_pick_actions.argtypes = [vp, vp, ci, vp, i64, u64, u32, u64, vp]
     L.pomdp_heuristic_steps.restype = ci
     L.pomdp_heuristic_steps.argtypes = [ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, u64, u32, u64, i64, ci, vp]
+    L.pomdp_heuristic_collect.restype = ci
+    L.pomdp_heuristic_collect.argtypes = [ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, ci, i64, u64, u32, u64, i64, ci, vp]
     L.pomdp_reset_where.restype = ci
     L.pomdp_reset_where.argtypes = [ci, vp, vp, vp, vp, vp, i64, u64, u32, u64, vp]
     L.pomdp_finish_episodes.restype = ci

@@ -1,7 +1,8 @@
-// planner.hip — planner hooks: _generate_legal, _compute_prob, fused rollouts, side statistics, History, _generate_preferred, the heuristic-policy loop.
+// planner.hip — planner hooks: _generate_legal, _compute_prob, fused rollouts, side statistics, History, _generate_preferred, the heuristic-policy loop (heuristic_impl.hip.h).
 // Part of libpomdp_hip.so; built by gym_pomdp_amd/_native.py (hipcc --offload-arch=gfx950 -O3 -std=c++17 -c, one object per file).
 #include "kernels_common.hip.h"
 #include "planner_common.hip.h"
+#include "heuristic_impl.hip.h"
 
 namespace pomdp {
 
@@ -112,58 +113,6 @@ __global__ __launch_bounds__(BLOCK) void select_target_kernel(const typename Env
     target[i] = Env::select_target(sh, p, st, b, n, (uint32_t)i);
 }
 
-// the two sums over CHECK-j transitions (rock.py:303-310, 327-334) and the derived bits j and 16 + j of move_ok: the contribution of
-// one transition (action CHECK j, next observation, observation before it) is added (sign = 1) or, when a bounded history
-// drops the transition, taken out again (sign = -1)
-static __device__ __forceinline__ void history_check_sums(const pomdp_history &h, int j, int next_ob, bool prev_bad, int64_t n,
-                                                          uint32_t i, uint32_t &mv, int sign = 1)   // mv: the caller's copy of h.move_ok[i]
-{
-    const int64_t k = (int64_t)j * n + i;
-    const int ds = sign * ((next_ob == 2) - (next_ob == 1));
-    const int dm = sign * (next_ob == 2 ? 1 : (prev_bad ? -1 : 0));
-    if (ds) {                                                                  // bit 16 + j: total_sample[j] > 0 (rock.py:311)
-        const int ts = h.total_sample[k] + ds;
-        h.total_sample[k] = ts;
-        const uint32_t sbit = 0x10000u << j;
-        mv = ts > 0 ? (mv | sbit) : (mv & ~sbit);
-    }
-    if (dm) {
-        const int tm = h.total_move[k] + dm;
-        h.total_move[k] = tm;
-        const uint32_t bit = 1u << j;
-        mv = tm >= 0 ? (mv | bit) : (mv & ~bit);
-    }
-}
-
-// history.append(transition) of rock.py:541-544 on the lane's words: `size` (the list length), the window of a bounded
-// history (max_size >= 0: one byte per kept transition — action | next_ob << 5 | (observation == BAD) << 7 — in a ring of
-// max_size + 1 rows, `head` = the row the next transition goes to, which holds the OLDEST one once the ring is full:
-// the reference pops element 0 when size > max_size and then appends, so the list settles at max_size + 1 records) and,
-// for RockSample (K > 0), the two per-rock sums kept current as transitions enter and leave the window.
-// A record leaves the sums with exactly what it entered them with ONLY for what the byte holds — an action in [0, 31] and a
-// next observation in [0, 3]: the caller hands in nothing else (the heuristic loop's come from the env; history_append_kernel
-// canonicalises the caller's int32s first).
-// RING = false: the caller knows there is no window to keep (an unbounded history, or an env without rocks) — the
-// heuristic loop is instantiated both ways so that the unbounded history does not carry the window's registers and branches.
-template <bool RING = true>
-static __device__ __forceinline__ void history_push(const pomdp_history &h, int K, int a, int next_ob, int prev_ob, int64_t n,
-                                                    uint32_t i, int &hsize, int &head, uint32_t &mv)
-{
-    const int W = h.max_size + 1;                                              // 0: unbounded
-    if (RING && W > 0 && K > 0) {
-        uint8_t *slot = h.ring + (int64_t)head * n + i;
-        if (hsize == W) {                                                      // self._history.pop(0)
-            const uint32_t old = *slot;
-            const int oa = (int)(old & 31u);
-            if (oa >= 5 && oa < 5 + K) history_check_sums(h, oa - 5, (int)((old >> 5) & 3u), (old >> 7) != 0u, n, i, mv, -1);
-        }
-        *slot = (uint8_t)((uint32_t)a | ((uint32_t)next_ob << 5) | ((prev_ob == 1) ? 128u : 0u));
-        head = head + 1 == W ? 0 : head + 1;
-    }
-    hsize = (W > 0 && hsize == W) ? W : hsize + 1;
-    if (a >= 5 && a < 5 + K) history_check_sums(h, a - 5, next_ob, prev_ob == 1, n, i, mv);
-}
-
 __global__ __launch_bounds__(BLOCK) void history_clear_kernel(pomdp_history h, int K, const uint8_t *__restrict__ where, int64_t n)
 {
     const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
@@ -242,186 +191,6 @@ __global__ __launch_bounds__(BLOCK) void pick_actions_kernel(const int32_t *__re
     const uint32_t word = e == 0 ? w.x : e == 1 ? w.y : e == 2 ? w.z : w.w;
     const int c = len[i];
     action[i] = c > 0 ? list[i * stride + (int64_t)__umulhi(word, (uint32_t)c)] : -1;
-}
-
-// RockSample envs maintain side statistics; the other envs have none
-template <class Env, class = void>
-struct BeliefOps {
-    static __device__ __forceinline__ void update(const typename Env::Shared &, const typename Env::Params &,
-                                                  const typename Env::State &, int, int, const pomdp_rock_belief &, int64_t,
-                                                  uint32_t, uint32_t &) {}
-};
-template <int W, bool STOCH>
-struct BeliefOps<RockEnv<W, STOCH>, void> {
-    using Env = RockEnv<W, STOCH>;
-    static __device__ __forceinline__ void update(const typename Env::Shared &sh, const typename Env::Params &p,
-                                                  const typename Env::State &st, int a, int o, const pomdp_rock_belief &b,
-                                                  int64_t n, uint32_t i, uint32_t &ck) { Env::belief_update(sh, p, st, a, o, b, n, i, ck); }
-};
-template <class Env>
-static __device__ __forceinline__ void heuristic_belief_update(const typename Env::Shared &sh, const typename Env::Params &p,
-                                                               const typename Env::State &st, int a, int o,
-                                                               const pomdp_rock_belief &b, int64_t n, uint32_t i, uint32_t &ck)
-{
-    BeliefOps<Env>::update(sh, p, st, a, o, b, n, i, ck);
-}
-
-
-// k heuristic-policy steps in one launch: per step choice(_generate_preferred(history)) -> step -> side statistics ->
-// history.append, i.e. preferred_kernel + pick_actions_kernel + step_kernel + belief_update_kernel +
-// history_append_kernel on the same call counter, with the lists never leaving registers.  Across the k steps a lane's
-// state, its history words (size, last action / observation, prev_ob), the two derived words and the running return stay
-// in registers and are written back once; the per-rock arrays are read and written in place when a CHECK touches them;
-// every step's action / ob / reward / done (and state) is written as the single-step launches write them.
-// Six waves per SIMD (at most 80 registers) where the compiler's own choice was five (81-86): the loop's CHECK / fresh-episode
-// branches stall on memory, and the sixth wave fills those slots — RockSample(7,8) 4.64 -> 4.52, (15,15) 5.98 -> 5.85, Tag
-// 4.35 -> 4.15 us per step at 2^20 lanes; four waves: 4.95 / 6.42 / 4.69, eight (spilling): 5.17 / 6.58 / 4.22.  BattleShip
-// (three state words and more) keeps the compiler's own choice — waves_per_eu(1) constrains nothing: 81-105 registers, five
-// or four waves; six would spill 100+ bytes per lane.  Every launch runs at least one step (the launcher's k >= 1): the
-// outputs written after the loop are those of the launch's last step.
-template <class Env> struct heur_waves { static constexpr int value = Env::WORDS <= 2 ? 6 : 1; };
-template <class Env, bool RING>   // RING: a bounded RockSample history (history_push keeps its window)
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(heur_waves<Env>::value)))
-void heuristic_steps_kernel(const typename Env::Params p, uint32_t *__restrict__ state,
-                                                                pomdp_rock_belief b, pomdp_history h, int K, pomdp_returns R,
-                                                                int32_t *__restrict__ prev_ob, int32_t *__restrict__ action,
-                                                                int32_t *__restrict__ ob, typename Env::Reward *__restrict__ reward,
-                                                                uint8_t *__restrict__ done, int64_t n, RngKey key0, uint32_t lane0,
-                                                                int flags, int k_steps)
-{
-#pragma clang fp contract(off)
-    // the number of rocks is 0 at compile time for the envs without rocks: their loop carries none of the per-rock code
-    // (Tag 4.03 -> 3.69 us per step, BattleShip 10 x 10 81 -> 72 registers; RockSample's own code is untouched — its
-    // allocation sits on the 80-register edge and any rewording of these lines has cost it 8 %)
-    K = Env::HAS_ROCKS ? K : 0;
-    __shared__ typename Env::Shared sh;
-    const bool auto_reset = flags & POMDP_AUTO_RESET;
-    const uint32_t idx = blockIdx.x * (uint32_t)BLOCK + threadIdx.x;
-    const bool in_range = (uint64_t)idx < (uint64_t)n;
-    const uint32_t i = in_range ? idx : (uint32_t)(n - 1);     // memory index only: threads past n read lane n - 1's words
-    // the lane id — and with it the quad element e that picks which step's quad-shared block this thread computes — comes
-    // from the UNCLAMPED index, as in rollout_kernel / steps_kernel: the padding threads of a ragged last quad (n % 4 != 0)
-    // still supply the blocks of steps base + 1 .. 3 to the quad's in-range lanes through quad_transpose4
-    const uint32_t lane = lane0 + idx;
-    // every per-lane word first (one memory latency), then the tables
-    typename Env::State st;
-    Env::load(st, state, n, i);
-    if constexpr (has_next<Env>::value) Env::load_next(st, state, n, i);
-    int hsize = ld_stream(h.size + i), pob = ld_stream(prev_ob + i), head = RING ? ld_stream(h.head + i) : 0;
-    int la = ld_stream(h.last_action + i), lo = ld_stream(h.last_ob + i);
-    uint32_t ck = K ? ld_stream(b.check_ok + i) : 0u, mv = K ? ld_stream(h.move_ok + i) : 0u;
-    bool was_done = auto_reset ? false : (ld_stream(done + i) != 0);
-    double ret = R.ret ? R.ret[i] : 0.0, disc = R.ret ? R.disc[i] : 1.0;
-    Env::stage(sh, p, (int)threadIdx.x);
-    stage_policy_tables<Env>(sh, p);
-    __syncthreads();
-    bool ever_fresh = false;
-    // what the launch's LAST step returns: every step overwrites the same n-element outputs, so only the last one's values
-    // are ever visible — they are written once, after the loop (round 4).  Inside the loop they were four stores per step
-    // that every CHECK's read-modify-write of the side statistics then waited behind (loads and stores share one counter).
-    int out_a = -1, out_o = 0, out_d = 0;
-    typename Env::Reward out_r = 0;
-    const int hcap = h.max_size >= 0 ? h.max_size + 1 : 0x7FFFFFFF;            // len(history) stops there (rock.py:541-544)
-    const uint64_t t0 = ((uint64_t)key0.t_hi << 32) | key0.t_lo;
-    const uint32_t e = lane & 3u;
-    // Random words four steps at a time, as in the rollout kernel: the policy's ACTION block is shared by the four lanes
-    // of a quad (and so is RockSample's STEP block), so lane e of a quad computes the block(s) of step base + e and the
-    // words travel by DPP quad-broadcast — one block per lane per four steps instead of four.
-    // (no priority ladder here — LoopPrio, kernels_common.hip.h: this loop's launches run several rounds of workgroups and
-    // its CHECK steps load; measured 2.17 -> 2.02e11 steps/s on RockSample(7,8) with it, no change on Tag)
-    for (int base = 0; base < k_steps; base += 4) {
-        const uint64_t te = t0 + (uint64_t)base + (uint64_t)e;
-        RngKey ke = key0;
-        ke.t_lo = (uint32_t)te; ke.t_hi = (uint32_t)(te >> 32);
-        const uint4 aq = quad_transpose4(stream_block(ke, lane >> 2, POMDP_STREAM_ACTION, 0u), e);   // .J: this lane's word of step base + J
-        uint4 sq = make_uint4(0, 0, 0, 0);
-        if constexpr (Env::QUAD_SENSOR) sq = quad_transpose4(Env::quad_block(ke, lane, 0u), e);
-        auto one_step = [&](auto jc) {
-            constexpr int J = decltype(jc)::value;
-            const int s = base + J;
-            if (s >= k_steps) return;                                          // wave-uniform
-            RngKey key = key0;
-            key.t_lo = (uint32_t)(t0 + (uint64_t)s); key.t_hi = (uint32_t)((t0 + (uint64_t)s) >> 32);
-            // the policy: a = list[(w * len(list)) >> 32] over the preferred list (ascending mask order) or the legal list
-            const uint32_t word = comp<J>(aq);
-            const uint32_t m = Env::preferred_mask(sh, p, st, h, n, i, ck, mv, hsize, la, lo);
-            int a;
-            if (m) a = nth_set_bit(m, (int)__umulhi(word, (uint32_t)__popc(m)));
-            else {
-                const auto L = LegalOf<Env>::make(sh, p, st, false);
-                a = LegalOf<Env>::pick(sh, p, st, L, (int)__umulhi(word, (uint32_t)L.count));
-            }
-            const bool live = in_range && !was_done;
-            const typename Env::State before = st;
-            int o, d;
-            typename Env::Reward r;
-            if constexpr (Env::QUAD_SENSOR) {
-                Env::step_with_H(sh, p, st, a, key, lane, comp<J>(sq), o, r, d);
-            } else {
-                Env::step(sh, p, st, a, key, lane, o, r, d);
-            }
-            if (!live) { o = 0; r = 0; d = was_done; st = before; }
-            const bool fresh = live && d && auto_reset;
-            if constexpr (Env::QUAD_SENSOR) {
-                // RockSample: the fresh episode starts from the word the step's sensor draw would have read (auto-reset
-                // contract, rock.hip.h) — this lane's word of the quad's block is already here; reset_where would compute
-                // that block again, per lane, in every wave-step in which some lane's episode ends
-                st.s = fresh ? Env::fresh_state(p, comp<J>(sq), key, lane) : st.s;
-            } else {
-                Env::reset_where(sh, p, st, fresh, key, lane);                 // wave-cooperative: every lane calls it
-            }
-            ever_fresh |= fresh;
-            if (live) {
-                if (R.ret) {                                                   // r += rw * discount; discount *= _discount
-                    const double term = disc * (double)r;
-                    const double acc = ret + term;
-                    if (d) R.ret_done[i] = acc;
-                    ret = fresh ? 0.0 : acc;
-                    disc = fresh ? 1.0 : disc * R.discount;
-                }
-                if (fresh) {                                                   // new episode: fresh Rock objects, empty History
-                    for (int j = 0; j < K; ++j) {
-                        const int64_t k = (int64_t)j * n + i;
-                        b.count[k] = 0; b.measured[k] = 0; b.lkv[k] = 1.; b.lkw[k] = 1.; b.prob_valuable[k] = .5;
-                        h.total_sample[k] = 0; h.total_move[k] = 0;
-                    }
-                    ck = mv = K ? (1u << K) - 1u : 0u;
-                    hsize = 0; la = -1; lo = -1; head = 0;
-                    pob = Env::reset_ob(p, st);
-                } else {
-                    la = a; lo = o;                                            // a terminal transition is recorded too
-                    if constexpr (RING) {
-                        history_push<true>(h, K, a, o, pob, n, i, hsize, head, mv);
-                        if (a >= 5 && a < 5 + K && o != 0 && !d) heuristic_belief_update<Env>(sh, p, st, a, o, b, n, i, ck);
-                    } else {                                                   // no window: history_push<false>, one CHECK branch
-                        hsize += (int)(hsize != hcap);
-                        if (a >= 5 && a < 5 + K) {                             // K > 0: RockSample CHECK
-                            history_check_sums(h, a - 5, o, pob == 1, n, i, mv);
-                            if (o != 0 && !d) heuristic_belief_update<Env>(sh, p, st, a, o, b, n, i, ck);
-                        }
-                    }
-                    pob = o;
-                }
-            }
-            out_a = live ? a : -1; out_o = o; out_r = r; out_d = d;
-            if (live) was_done = auto_reset ? false : (d != 0);
-        };
-        one_step(std::integral_constant<int, 0>{});
-        one_step(std::integral_constant<int, 1>{});
-        one_step(std::integral_constant<int, 2>{});
-        one_step(std::integral_constant<int, 3>{});
-    }
-    if (!in_range) return;
-    st_stream(action + i, (int32_t)out_a);
-    st_stream(ob + i, (int32_t)out_o);
-    st_stream(reward + i, out_r);
-    st_stream(done + i, (uint8_t)out_d);
-    Env::store(st, state, n, i, ever_fresh);                                   // the loop's carry, written once
-    st_stream(h.size + i, (int32_t)hsize); st_stream(h.last_action + i, (int32_t)la); st_stream(h.last_ob + i, (int32_t)lo);
-    st_stream(prev_ob + i, (int32_t)pob);
-    if (K) { st_stream(b.check_ok + i, ck); st_stream(h.move_ok + i, mv); }
-    if (RING) st_stream(h.head + i, (int32_t)head);                            // without a window `head` never moves
-    if (R.ret) { R.ret[i] = ret; R.disc[i] = disc; }
 }
 
 // Lane i simulates from root state column i / sims_per_root for up to `depth` steps: the state lives in registers
@@ -644,8 +413,6 @@ static int launch_rollout(const typename Env::Params &p, const uint32_t *state, 
                        n_steps, first_action, last_ob, terminated);
     return (int)hipGetLastError();
 }
-static const pomdp_rock_belief NO_BELIEF = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-
 template <class Env>
 static int launch_belief_update(const typename Env::Params &p, const uint32_t *state, const int32_t *action, const int32_t *ob,
                                 const uint8_t *done, const pomdp_rock_belief *b, int64_t n, int flags, void *stream)
@@ -672,34 +439,6 @@ static int launch_preferred(const typename Env::Params &p, const uint32_t *state
     hipLaunchKernelGGL(preferred_kernel<Env>, dim3(blocks_for(n)), dim3(BLOCK), 0, (hipStream_t)stream, p, state,
                        b ? *b : NO_BELIEF, *h, list, len, n, stride);
     return (int)hipGetLastError();
-}
-template <class Env>
-static int launch_heuristic_steps(const typename Env::Params &p, uint32_t *state, const pomdp_rock_belief *b,
-                                  const pomdp_history *h, int K, int32_t *prev_ob, int32_t *action, int32_t *ob, void *reward,
-                                  uint8_t *done, const pomdp_returns *returns, int64_t n, uint64_t seed, uint32_t lane0,
-                                  uint64_t t0, int64_t k_steps, int flags, void *stream)
-{
-    if (n == 0) return 0;
-    static const pomdp_returns NO_RETURNS = {0.0, nullptr, nullptr, nullptr};
-    const int64_t FUSE_MAX = fuse_max();                  // steps per launch
-    for (int64_t s = 0; s < k_steps; s += FUSE_MAX) {
-        const int c = (int)(k_steps - s < FUSE_MAX ? k_steps - s : FUSE_MAX);
-        bool ring = false;
-        if constexpr (Env::HAS_ROCKS) ring = h->max_size >= 0 && K > 0 && h->ring && h->head;
-        if constexpr (Env::HAS_ROCKS) {
-            if (ring)
-                hipLaunchKernelGGL((heuristic_steps_kernel<Env, true>), dim3(blocks_for(n)), dim3(BLOCK), 0, (hipStream_t)stream, p,
-                                   state, b ? *b : NO_BELIEF, *h, K, returns ? *returns : NO_RETURNS, prev_ob, action, ob,
-                                   (typename Env::Reward *)reward, done, n, make_key(seed, t0 + (uint64_t)s), lane0, flags, c);
-        }
-        if (!ring)
-            hipLaunchKernelGGL((heuristic_steps_kernel<Env, false>), dim3(blocks_for(n)), dim3(BLOCK), 0, (hipStream_t)stream, p,
-                               state, b ? *b : NO_BELIEF, *h, K, returns ? *returns : NO_RETURNS, prev_ob, action, ob,
-                               (typename Env::Reward *)reward, done, n, make_key(seed, t0 + (uint64_t)s), lane0, flags, c);
-        const int rc = (int)hipGetLastError();
-        if (rc) return rc;
-    }
-    return 0;
 }
 
 } // namespace pomdp
@@ -802,13 +541,6 @@ int pomdp_rock_select_target(const pomdp_rock_params *p, const uint32_t *state, 
     return launch_select_target<RockEnv<2>>(*p, state, b, target, n, stream);
 }
 
-static int history_rocks(int env, const void *params)
-{
-    if (env != POMDP_ENV_ROCK) return (env >= POMDP_ENV_TAG && env <= POMDP_ENV_NETWORK) ? 0 : -1;
-    const pomdp_rock_params *p = (const pomdp_rock_params *)params;
-    return (p && rock_ok(p)) ? p->num_rocks : -1;
-}
-
 int pomdp_history_clear(int env, const void *params, const pomdp_history *h, const uint8_t *where, int64_t n, void *stream)
 {
     const int K = history_rocks(env, params);
@@ -858,12 +590,7 @@ int pomdp_heuristic_steps(int env, const void *params, uint32_t *state, const po
                           int64_t k_steps, int flags, void *stream)
 {
     const int K = history_rocks(env, params);
-    // (the policy's block — and RockSample's STEP / RESET blocks — are shared by global lanes 4 q .. 4 q + 3 and travel
-    // within the hardware quad: a shard has to start on such a boundary)
-    if (K < 0 || !params || !state || !prev_ob || !action || !ob || !reward || !done || k_steps < 0 || bad_range(n, lane0) || (lane0 & 3u))
-        return POMDP_E_BADARG;
-    if (!history_ok(h, K > 0) || (K > 0 && !belief_ok(b))) return POMDP_E_BADARG;
-    if (returns && !(returns->ret && returns->disc && returns->ret_done)) return POMDP_E_BADARG;
+    if (!heuristic_args_ok(K, params, state, b, h, prev_ob, action, ob, reward, done, returns, n, lane0, k_steps)) return POMDP_E_BADARG;
     return dispatch_env(env, params, [&](auto tag, const auto &p) {
         using E = typename decltype(tag)::Env;
         return launch_heuristic_steps<E>(p, state, b, h, K, prev_ob, action, ob, reward, done, returns, n, seed, lane0, t0,

@@ -580,6 +580,53 @@ class BatchedEnv(compat.EnvBase):
             _native.check(rc, "pomdp_heuristic_steps")
         return self._action_scratch, self._ob, self._reward, self._done.view(torch.bool)
 
+    def collect_heuristic(self, history, steps, layout="packed", out=None, returns=None):
+        """heuristic_steps(history, steps) with every step kept (pomdp_heuristic_collect): the same launches leave the env,
+        `history`, the side statistics, `returns` and the last step's `_ob / _reward / _done` buffers exactly as
+        heuristic_steps does, and row s of the trajectory holds what the policy did at step s — the reference's `history[t]`
+        (rock.py:525-550) for every lane: the action it chose, the observation, the reward and done.
+        `layout`: "packed" (one 4-byte record per lane-step) or "narrow" (four typed planes per step), as in
+        collect_synthetic.  `out`: a dict of trajectory_buffers(k, layout) with k >= steps, reused without allocation; only
+        rows 0 .. steps - 1 are written.  Returns that dict: decode_trajectory(out, steps) gives the four columns.
+        With auto_reset a done row carries the terminal observation; the observation the fresh episode starts with is NOT
+        recorded (history.prev_ob holds it after a launch that ends there).  Without auto_reset a lane whose episode ended
+        earlier is frozen: its records are 0x010000FF — action 255 (heuristic_steps reports -1), ob 0, reward 0, done True.
+        Asynchronous."""
+        if not self._has_reset:
+            raise AttributeError("%s: collect_heuristic before reset()" % type(self).__name__)
+        if history.prev_ob is None:
+            raise ValueError("History was built without the current observation: History(env, observation=ob)")
+        if self.lane_offset % 4:
+            raise ValueError("collect_heuristic: lane_offset must be a multiple of 4 (got %d): the policy's Philox block is shared "
+                             "by global lanes 4q .. 4q+3" % self.lane_offset)
+        if layout not in ("packed", "narrow"):
+            raise ValueError("collect_heuristic: layout must be 'packed' or 'narrow', got %r" % (layout,))
+        steps = int(steps)
+        if steps < 0:
+            raise ValueError("collect_heuristic: steps must be >= 0")
+        if out is None:
+            out = self.trajectory_buffers(steps, layout)
+        elif out.get("layout") != layout or out["traj"].shape[0] < steps or out["pitch"] < self.batch_size \
+                or out["traj"].shape[-1] != out["pitch"] or out["traj"].device != self.device:
+            raise ValueError("collect_heuristic: `out` is not a trajectory_buffers(k >= %d, %r) dict of this env" % (steps, layout))
+        if steps == 0:
+            return out
+        if getattr(self, "_action_scratch", None) is None:
+            self._action_scratch = torch.empty(self.batch_size, dtype=torch.int32, device=self.device)
+        t0 = self._t
+        self._t += steps
+        self._dev_flags_used = True
+        with torch.cuda.device(self.device):
+            rc = self._lib.pomdp_heuristic_collect(
+                _native.ENV_KIND[self.env_name], self._params_ref, self._state.data_ptr(),
+                self._belief_ref() if self.env_name == "rock" else None, history._ref, history.prev_ob.data_ptr(),
+                self._action_scratch.data_ptr(), self._ob.data_ptr(), self._reward.data_ptr(), self._done.data_ptr(),
+                None if returns is None else returns._ref, out["traj"].data_ptr(), int(out["pitch"]), _native.LAYOUTS[layout],
+                self.batch_size, self._seed, self.lane_offset, t0, steps,
+                _native.POMDP_AUTO_RESET if self.auto_reset else 0, self._stream())
+            _native.check(rc, "pomdp_heuristic_collect")
+        return out
+
     def compute_prob(self, action, ob, state=None):
         """`_compute_prob(action, next_state, ob)` per lane -> float64[N]: the likelihood of `ob` given that
         `action` led to `state` (default: the live state)."""

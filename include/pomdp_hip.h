@@ -678,6 +678,28 @@ int pomdp_heuristic_steps(int env, const void *params, uint32_t *state, const po
                           const pomdp_returns *returns, int64_t n, uint64_t seed, uint32_t lane0, uint64_t t0,
                           int64_t k_steps, int flags, void *stream);
 
+/* pomdp_heuristic_steps with every step kept (added to ABI 15: a new entry point only, nothing existing changes): the same
+ * loop on the same arguments leaves, bit for bit, what pomdp_heuristic_steps leaves — state, prev_ob, the history words,
+ * sums and ring, RockSample's side statistics and derived words, the last step's action / ob / reward / done, `returns` —
+ * and in addition row s of `traj` holds step t0 + s of every lane, in one of the two 4-byte layouts of pomdp_collect_layout:
+ *   POMDP_LAYOUT_PACKED   traj uint32 [k_steps][pitch], pitch >= n;
+ *   POMDP_LAYOUT_NARROW   traj uint8 [k_steps][4][pitch], pitch >= n and a multiple of 4 (and at most (2^32 - 256) / 3: a
+ *                         thread's offset within a row is a 32-bit word); the bytes of the lanes n .. up to the next
+ *                         multiple of 4 are written as 0, nothing beyond them is touched.
+ * The record of a live lane-step is  action | ob << 8 | reward_code << 16 | done << 24  with the action the policy chose and
+ * the reward code of pomdp_collect_layout (Network: the table index).  With POMDP_AUTO_RESET a done row carries the TERMINAL
+ * observation, as in every auto-reset sink; the observation the fresh episode starts with is not recorded (it is what
+ * prev_ob holds for the lane if the launch ends there, and what reset() of that (seed, lane, t) returns).  Without
+ * POMDP_AUTO_RESET a lane whose `done` was set before step s is frozen and its record is 0x010000FF: action byte 0xFF (the -1
+ * pomdp_heuristic_steps reports for it; no env has 255 actions), ob 0, reward 0, done 1.
+ * POMDP_E_BADARG before any launch: traj == NULL, pitch < n, a NARROW pitch that is not a multiple of 4, any other layout
+ * (COLUMNS and BLOCKED included), lane0 % 4 != 0 and everything pomdp_heuristic_steps refuses.  k_steps == 0 is a no-op;
+ * longer calls are split at pomdp_fuse_max() steps per launch, and the rows never depend on the split. */
+int pomdp_heuristic_collect(int env, const void *params, uint32_t *state, const pomdp_rock_belief *b, const pomdp_history *h,
+                            int32_t *prev_ob, int32_t *action, int32_t *ob, void *reward, uint8_t *done,
+                            const pomdp_returns *returns, void *traj, int64_t pitch, int layout,
+                            int64_t n, uint64_t seed, uint32_t lane0, uint64_t t0, int64_t k_steps, int flags, void *stream);
+
 /* ---- rollouts under the env's preferred-action policy (added to ABI 15: new entry points only, nothing existing changes) --
  * pomdp_rollout with a different list to pick from: POMCP's rollout policy.  The lanes, the ROLLOUT word k that picks, the
  * STEP words at t0 + k, the float64 return (separate multiply and add) and the outputs ret / n_steps / first_action /

@@ -7,7 +7,8 @@
 #   sets (default "planners headline envs"): planners = rollouts + heuristic loops; headline = RockSample(7,8) in every sink
 #   (packed, columns, blocked, narrow, returns) x (256, 20) steps per launch + HBM byte passes; envs = the other envs' fused
 #   launches (packed and columns); shards = RockSample(7,8) at 2^17 / 2^18 / 2^19 lanes; packed = the headline kernel alone
-#   (RockSample(7,8), packed records, both launch shapes) with its HBM byte passes: what a change to the lane step re-records.
+#   (RockSample(7,8), packed records, both launch shapes) with its HBM byte passes: what a change to the lane step re-records;
+#   heuristic = the heuristic loops of `planners` without the rollouts.
 #   Workloads that are not re-recorded are carried over from the newest profiles/*_pmc_valu.json, each with the source hash
 #   it was recorded under (bench.py: counters_stale).
 TAG=${1:-pmcv}
@@ -26,6 +27,7 @@ pass() {   # log, command...: one profiled run under its own time limit; a run t
   timeout -k 10 600 "$@" > $log 2>&1
   local rc=$?
   case $rc in 124|134|137|139) echo "pass ended with status $rc ($log): stopping"; tail -5 $log; exit $rc ;; esac
+  echo "pass ${log#$W/}: status $rc"      # (a line per pass: a long set shows that it is alive)
 }
 run() {   # name, bench args...
   local name=$1; shift
@@ -50,6 +52,14 @@ traffic() {   # name, bench args...: FETCH_SIZE and WRITE_SIZE in separate passe
   pass $W/$name/f.log rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $W/$name/pmc_fetch -o f -- python $REPO/bench.py "$@"
   pass $W/$name/w.log rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $W/$name/pmc_write -o w -- python $REPO/bench.py "$@"
 }
+heuristic_loops() {
+    run heuristic_rock --env rock --mode heuristic --prewarm 0 --warmup 128 --steps 1024
+    run heuristic_rock15 --env rock15 --mode heuristic --prewarm 0 --warmup 128 --steps 1024
+    run heuristic_tag --env tag --mode heuristic --prewarm 0 --warmup 128 --steps 1024
+    # what the heuristic loop's CHECKs move: the side statistics are seven [K][N] arrays read-modify-written per CHECK
+    traffic heuristic_rock15 --env rock15 --mode heuristic --prewarm 0 --warmup 128 --steps 1024
+    traffic heuristic_rock --env rock --mode heuristic --prewarm 0 --warmup 128 --steps 1024
+}
 sfx() { if [ "$1" = columns ]; then echo ""; else echo "_$1"; fi; }
 S256="--prewarm 0 --warmup 256 --steps 1024 --seeds 0 --repeats 1 --no-cpu-baseline --no-extras"
 S20="--gpus 1 --steps 20 --warmup 5 --prewarm 0 --seeds 0 --no-cpu-baseline --no-extras"
@@ -59,12 +69,9 @@ for set in $SETS; do
     run rollout_rock15 --env rock15 --mode rollout --lanes-per-gpu 2097152 --steps 20 --warmup 10
     run rollout_rock --env rock --mode rollout --lanes-per-gpu 2097152 --steps 20 --warmup 10
     run rollout_tag --env tag --mode rollout --lanes-per-gpu 2097152 --steps 20 --warmup 10
-    run heuristic_rock --env rock --mode heuristic --prewarm 0 --warmup 128 --steps 1024
-    run heuristic_rock15 --env rock15 --mode heuristic --prewarm 0 --warmup 128 --steps 1024
-    run heuristic_tag --env tag --mode heuristic --prewarm 0 --warmup 128 --steps 1024
-    # what the heuristic loop's CHECKs move: the side statistics are seven [K][N] arrays read-modify-written per CHECK
-    traffic heuristic_rock15 --env rock15 --mode heuristic --prewarm 0 --warmup 128 --steps 1024
-    traffic heuristic_rock --env rock --mode heuristic --prewarm 0 --warmup 128 --steps 1024 ;;
+    heuristic_loops ;;
+  heuristic)
+    heuristic_loops ;;
   headline)
     for l in packed columns blocked narrow returns; do
       k=256; if [ $l = columns ] || [ $l = blocked ]; then k=64; fi      # pomdp_fuse_steps: RockSample's 13-byte layouts stay at 64

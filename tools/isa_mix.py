@@ -310,7 +310,10 @@ def main():
         sys.path.insert(0, REPO)
         from bench import csrc_sha                      # the sources this mix was compiled from (bench.py: counters_stale)
         res["csrc_sha256"] = csrc_sha()
-        json.dump(res, open(out_json, "w"), indent=1)
+        # one kernel per line: a re-recorded file differs from the one before it only in the kernels that changed
+        kernels = res.pop("kernels")
+        rows = ",\n".join("  %s: %s" % (json.dumps(k), json.dumps(v)) for k, v in kernels.items())
+        open(out_json, "w").write('%s,\n "kernels": {\n%s\n }\n}\n' % (json.dumps(res, indent=1)[:-2], rows))
 
 
 if __name__ == "__main__":

@@ -30,6 +30,13 @@ MIN_WINDOW_US = 150.0        # launches shorter than this do not fill the GRBM c
 KERNELS = ("%rollout_kernel%", "%heuristic_steps_kernel%", "%steps%kernel%")
 
 
+def write_json(res, path):
+    """One workload per line: a re-recorded file differs from the one before it only in the workloads that were recorded again."""
+    head = {k: v for k, v in res.items() if k != "workloads"}
+    rows = ",\n".join("  %s: %s" % (json.dumps(k), json.dumps(v)) for k, v in res["workloads"].items())
+    open(path, "w").write('%s,\n "workloads": {\n%s\n }\n}\n' % (json.dumps(head, indent=1)[:-2], rows))
+
+
 def db_of(d):
     f = glob.glob(os.path.join(d, "**", "*_results.db"), recursive=True)
     return f[0] if f else None
@@ -167,7 +174,7 @@ def main():
                 entry.setdefault("csrc_sha256", old.get("csrc_sha256"))
                 res["workloads"][name] = entry
     os.makedirs(out_dir, exist_ok=True)
-    json.dump(res, open(os.path.join(out_dir, "pmc_valu.json"), "w"), indent=1)
+    write_json(res, os.path.join(out_dir, "pmc_valu.json"))
     with open(os.path.join(out_dir, "pmc_valu.txt"), "w") as fo:
         fo.write("# tools/gpu_pmc_valu.sh — rocprofv3 --pmc passes (MI355X); issue peak = 256 x 4 x 2.4e9 / 4 = %.4e wave-instructions/s\n" % ISSUE_PEAK)
         for name, cmd in cmds.items():
