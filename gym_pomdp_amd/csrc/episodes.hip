@@ -232,8 +232,9 @@ __global__ __launch_bounds__(BLOCK) void episodes_quad_kernel(uint32_t *__restri
     __shared__ typename Env::RecTab tab;
     const uint32_t n_act = (uint32_t)Env::n_actions(p);
     const uint32_t l0 = blockIdx.x * (uint32_t)(4 * BLOCK) + 4u * threadIdx.x, glane0 = lane0 + l0;
-    // the policy of step s is that of call counter t0 + s: SyntheticQuad::begin(s) with akey0 = key0
-    Pol pol(tape, l0, glane0, key0, key0, n_act, k_steps);
+    // the policy of step s is that of call counter t0 + s: SyntheticQuad::begin(s) with akey0 = key0 (its block's round-3
+    // product stays in the step: this loop does not run as stretches)
+    typename lanes_policy<Pol, 4, false>::type pol(tape, l0, glane0, key0, key0, n_act, k_steps);
     using Out = typename std::conditional<RETS, EpisodeReturns<Env, 4>, QuadOut<L>>::type;
     Out out = [&]() {
         if constexpr (RETS) return Out(reinterpret_cast<double *>(out0), reinterpret_cast<uint32_t *>(out1), bits_f64(discount_bits), rec);

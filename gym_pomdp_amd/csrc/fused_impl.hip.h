@@ -10,12 +10,16 @@ namespace pomdp {
 // The thread's place in the batch, its sink and its policy; the prologue around the first actions; the per-step key; the
 // epilogue of a step (the policy's next actions become the current ones) and of the launch.  LPT lanes per thread: 4, or 2
 // for BattleShip's small shards.  A contract change touches this and the env's own lane step, not six loops.
-template <class L, class Pol, int LPT = 4, bool SROW = false>   // SROW: packed records leave through a scalar row base (traj_out.hip.h)
+// HOIST: the policy's block takes round 3's product from in front of the step loop (philox.hip.h) — two more registers across
+// the loop.  The returns sinks of StochasticRock and BattleShip sit at 120-128 registers, four waves per SIMD (their sink keeps
+// 40 per thread): they keep the product in the step (hoist_fits), and so does the gate and sensor block of the former.
+template <class L, bool TIGHT> constexpr bool hoist_fits = !(TIGHT && L::ID == LAYOUT_RETURNS);
+template <class L, class Pol, int LPT = 4, bool SROW = false, bool HOIST = true>   // SROW: packed records leave through a scalar row base (traj_out.hip.h)
 struct FusedCtx {
     uint32_t l0, glane0;                                     // the thread's first lane within the shard / its global id
     uint64_t t0;                                             // call counter of the launch's first step
     typename lanes_out<L, LPT, SROW>::type out;
-    typename lanes_policy<Pol, LPT>::type pol;
+    typename lanes_policy<Pol, LPT, HOIST>::type pol;
     uint32_t n_bad;                                          // tape only: out-of-range actions met
     __device__ __forceinline__ FusedCtx(int32_t *action, int32_t *ob, void *reward, uint8_t *done, int64_t rec, uint32_t lane0,
                                         const RngKey &key0, const RngKey &akey0, uint32_t n_act, int k_steps, const TapeRef &tape)
@@ -36,6 +40,8 @@ struct FusedCtx {
             for (int j = 0; j < LPT; ++j) a_cur[j] = (int)a2[j];
         }
     }
+    // a stretch of the step loop from step s: the policy's products for it, and where it ends (at `end` or sooner)
+    __device__ __forceinline__ int stretch(int s, int end) { return pol.stretch(s, end); }
     // the env's Philox key at step s of the launch
     __device__ __forceinline__ RngKey key(const RngKey &key0, int s) const
     {
@@ -57,11 +63,14 @@ struct FusedCtx {
     }
 };
 // The step loop of a fused launch: every load issued so far has landed (wait_loads: a storing loop may not wait on vmcnt), then
-// four consecutive segments of falling issue priority (LoopPrio).  `s` runs over the launch's steps.
-#define POMDP_FUSED_STEP_LOOP(prio_, s_)                                                                              \
+// four consecutive segments of falling issue priority (LoopPrio), each run as stretches over which the call counters keep their
+// high words (`stretch_(s, seg_end)`: derives the hoisted Philox products for step s on and returns where they stop holding —
+// philox.hip.h; one stretch per segment unless a counter crosses a multiple of 2^32 in it).  `s` runs over the launch's steps.
+#define POMDP_FUSED_STEP_LOOP(prio_, s_, stretch_)                                                                    \
     wait_loads();                                                                                                      \
     _Pragma("unroll 1") for (int seg_ = 0, s_ = 0; seg_ < 4; ++seg_)                                                   \
-        for (const int seg_end_ = (prio_).segment(seg_); s_ < seg_end_; ++s_)
+        _Pragma("unroll 1") for (const int seg_end_ = (prio_).segment(seg_); s_ < seg_end_;)                           \
+            _Pragma("unroll 1") for (const int end_ = stretch_(s_, seg_end_); s_ < end_; ++s_)
 
 // k consecutive chained steps in ONE launch: exactly the memory state k launches of step_kernel<Env, LPT, true> leave —
 // every step's ob / reward / done / state / next action is computed and written — but a lane's state and action stay in
@@ -386,7 +395,8 @@ __device__ __forceinline__ void steps_quad_body(uint32_t *__restrict__ state, in
     // a quad per thread on a tape: the loop unrolled by two, the tape read two steps ahead (TapeQuadAhead)
     constexpr bool AHEAD2 = Pol::TAPE && LPT == 4;
     using PolT = typename std::conditional<AHEAD2, TapeQuadAhead, Pol>::type;
-    FusedCtx<L, PolT, LPT, true> cx(action, ob, reward, done, rec, lane0, key0, akey0, n_act, k_steps, tape);
+    constexpr bool HOIST = hoist_fits<L, Env::STOCHASTIC>;
+    FusedCtx<L, PolT, LPT, true, HOIST> cx(action, ob, reward, done, rec, lane0, key0, akey0, n_act, k_steps, tape);
     const uint32_t l0 = cx.l0, glane0 = cx.glane0;           // the thread's first lane within the shard; its global id (a multiple of LPT)
     const uint32_t e0 = LPT == 4 ? 0u : (glane0 & 2u);       // ... and that lane's element of its quad's blocks (LPT = 2: 0 or 2)
     typename Env::State st[LPT];
@@ -428,8 +438,28 @@ __device__ __forceinline__ void steps_quad_body(uint32_t *__restrict__ state, in
     const LoopPrio prio(k_steps);
     constexpr uint32_t SENSOR_BLOCK = Env::SENSOR_BLOCK;
     // a quad per thread: the quad's STEP blocks have counter words 0 and 3 fixed for the launch (philox4x32_10_fixed)
-    const PhiloxFixed sensor_fx = philox_fixed(glane0 >> 2, ((uint32_t)POMDP_STREAM_STEP << 24) | SENSOR_BLOCK, key0.k1);
-    const PhiloxFixed gate_fx = philox_fixed(glane0 >> 2, (uint32_t)POMDP_STREAM_STEP << 24, key0.k1);
+    // — with round 3's product hoisted for the stretch of steps that shares the counter's high word; the loop unrolled by two
+    // keeps one product per parity of the step, so that its stretches end at even steps
+    constexpr int NFX = AHEAD2 ? 2 : 1;
+    PhiloxFixed sensor_fx[NFX], gate_fx[NFX];
+#pragma unroll
+    for (int h = 0; h < NFX; ++h) {
+        sensor_fx[h] = philox_fixed(glane0 >> 2, ((uint32_t)POMDP_STREAM_STEP << 24) | SENSOR_BLOCK, key0.k1);
+        gate_fx[h] = philox_fixed(glane0 >> 2, (uint32_t)POMDP_STREAM_STEP << 24, key0.k1);
+    }
+    auto stretch = [&](const int s, int end) __attribute__((always_inline)) {
+        end = cx.stretch(s, end);
+        if constexpr (LPT == 4 && HOIST) {
+#pragma unroll
+            for (int h = 0; h < NFX; ++h) {
+                const RngKey kh = cx.key(key0, s + h);
+                philox_hoist(sensor_fx[h], kh.t_hi, kh.k0);
+                if constexpr (Env::STOCHASTIC) philox_hoist(gate_fx[h], kh.t_hi, kh.k0);
+                end = stretch_end<NFX>(s, end, kh.t_lo);
+            }
+        }
+        return end;
+    };
     if constexpr (W == 1) tie_bound = Form::tie_bound(K);
     auto step_body = [&](const int s, const auto par_) __attribute__((always_inline)) {
         constexpr int PAR = decltype(par_)::value;           // AHEAD2: s & 1
@@ -438,7 +468,7 @@ __device__ __forceinline__ void steps_quad_body(uint32_t *__restrict__ state, in
         // — the words its fresh episodes start from as well — and the actions of the next call counter
         uint32_t H[LPT], G[LPT];
         if constexpr (LPT == 4) {
-            const uint4 sw = philox4x32_10_fixed(sensor_fx, key.t_lo, key.t_hi, key.k0, key.k1);
+            const uint4 sw = philox4x32_10_fixed<HOIST>(sensor_fx[AHEAD2 ? PAR : 0], key.t_lo, key.t_hi, key.k0, key.k1);
             H[0] = sw.x; H[1] = sw.y; H[2] = sw.z; H[3] = sw.w;
         } else {
             pair_shared(s, e0 != 0u, [&](int sb) { return Env::quad_block(cx.key(key0, sb), glane0, SENSOR_BLOCK); }, H, sp0, sp1);
@@ -452,7 +482,7 @@ __device__ __forceinline__ void steps_quad_body(uint32_t *__restrict__ state, in
         for (int j = 0; j < LPT; ++j) acts[j] = true;
         if constexpr (Env::STOCHASTIC) {                                       // the action is applied iff binomial(1, p_move) says so
             if constexpr (LPT == 4) {
-                const uint4 gw = philox4x32_10_fixed(gate_fx, key.t_lo, key.t_hi, key.k0, key.k1);
+                const uint4 gw = philox4x32_10_fixed<HOIST>(gate_fx[AHEAD2 ? PAR : 0], key.t_lo, key.t_hi, key.k0, key.k1);
                 G[0] = gw.x; G[1] = gw.y; G[2] = gw.z; G[3] = gw.w;
             } else {
                 pair_shared(s, e0 != 0u, [&](int sb) { return Env::quad_block(cx.key(key0, sb), glane0, 0u); }, G, gp0, gp1);
@@ -547,12 +577,13 @@ __device__ __forceinline__ void steps_quad_body(uint32_t *__restrict__ state, in
     if constexpr (AHEAD2) {
         wait_loads();
         _Pragma("unroll 1") for (int seg = 0, s = 0; seg < 4; ++seg)           // (LoopPrio's segments, ending at even steps)
-            for (const int seg_end = prio.template segment<2>(seg); s < seg_end; s += 2) {
-                step_body(s, std::integral_constant<int, 0>{});
-                if (s + 1 < seg_end) step_body(s + 1, std::integral_constant<int, 1>{});
-            }
+            _Pragma("unroll 1") for (const int seg_end = prio.template segment<2>(seg); s < seg_end;)
+                _Pragma("unroll 1") for (const int end = stretch(s, seg_end); s < end; s += 2) {   // (stretches end at even steps too)
+                    step_body(s, std::integral_constant<int, 0>{});
+                    if (s + 1 < end) step_body(s + 1, std::integral_constant<int, 1>{});
+                }
     } else {
-        POMDP_FUSED_STEP_LOOP(prio, s) step_body(s, std::integral_constant<int, 0>{});
+        POMDP_FUSED_STEP_LOOP(prio, s, stretch) step_body(s, std::integral_constant<int, 0>{});
     }
     // the state is the loop's carry: it reaches memory once (one state word: back in its memory layout)
     cx.finish(k_steps);
@@ -613,7 +644,9 @@ __global__ __launch_bounds__(BLOCK) void tag_steps_quad_kernel(uint32_t *__restr
     __shared__ Env::Shared sh;
     __shared__ typename std::conditional<TAB, Env::StepTab, NoTab>::type tab;
     const uint32_t n_act = (uint32_t)Env::n_actions(p);
-    FusedCtx<L, Pol, LPT> cx(action, ob, reward, done, rec, lane0, key0, akey0, n_act, k_steps, tape);
+    // (the narrow sink's loop pays the hoisted product with three register moves: 450 vector instructions for 449, the same
+    // priced cycles — it keeps the product in the step)
+    FusedCtx<L, Pol, LPT, false, L::ID != POMDP_LAYOUT_NARROW> cx(action, ob, reward, done, rec, lane0, key0, akey0, n_act, k_steps, tape);
     const uint32_t l0 = cx.l0, glane0 = cx.glane0;
     const uint32_t e0 = LPT == 4 ? 0u : (glane0 & 2u);       // the first lane's element of its quad's blocks
     Env::State st[LPT];
@@ -639,7 +672,7 @@ __global__ __launch_bounds__(BLOCK) void tag_steps_quad_kernel(uint32_t *__restr
         __syncthreads();
     }
     const LoopPrio prio(k_steps);
-    POMDP_FUSED_STEP_LOOP(prio, s) {
+    POMDP_FUSED_STEP_LOOP(prio, s, cx.stretch) {
         const RngKey key = cx.key(key0, s);
         uint32_t a_next[LPT];
         cx.pol.begin(s, a_next);
@@ -776,7 +809,7 @@ __global__ __launch_bounds__(BLOCK) void network_steps_quad_kernel(uint32_t *__r
     const uint32_t all_up = p.n_machines >= 32 ? 0xFFFFFFFFu : ((1u << p.n_machines) - 1u);
     const int M2 = 2 * p.n_machines;
     const LoopPrio prio(k_steps);
-    POMDP_FUSED_STEP_LOOP(prio, s) {
+    POMDP_FUSED_STEP_LOOP(prio, s, cx.stretch) {
         const RngKey key = cx.key(key0, s);
         uint32_t a_next[4];
         cx.pol.begin(s, a_next);
@@ -950,7 +983,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(quad_wave
     Env::stage_seq(seq, p, (int)threadIdx.x);
     const int wv = (int)(threadIdx.x >> 6), me = (int)(threadIdx.x & 63u), tid = (int)threadIdx.x;
     const uint32_t n_act = (uint32_t)Env::n_actions(p);
-    FusedCtx<L, Pol, LPT> cx(action, ob, reward, done, rec, lane0, key0, akey0, n_act, k_steps, tape);
+    FusedCtx<L, Pol, LPT, false, hoist_fits<L, true>> cx(action, ob, reward, done, rec, lane0, key0, akey0, n_act, k_steps, tape);
     const uint32_t l0 = cx.l0, glane0 = cx.glane0, wave0 = glane0 - (uint32_t)LPT * (uint32_t)me;
     int rem[LPT];                                            // VIS_LDS: total_remaining (battleship.py:100-104)
     Mask vis[VIS_LDS ? 1 : LPT];                             // !VIS_LDS: the visited mask, remaining in the top bits of its last word
@@ -1039,7 +1072,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(quad_wave
     // is store-bound, and waves that leave the loop at different times build their boards under the others' stores (10x10,
     // 20 steps per launch: 5.8 us per step without the ladder, 6.3 with it; 5x5 at 64 steps: 5.0 without, 4.3 with).
     const LoopPrio prio(k_steps, k_steps >= 32);
-    POMDP_FUSED_STEP_LOOP(prio, s) {
+    POMDP_FUSED_STEP_LOOP(prio, s, cx.stretch) {
         uint32_t a_taken[LPT];
         bool valid[LPT];
 #pragma unroll
@@ -1168,7 +1201,7 @@ __global__ __launch_bounds__(BLOCK) void steps_quad_generic_kernel(uint32_t *__r
     Env::stage(sh, p, (int)threadIdx.x);
     __syncthreads();
     const LoopPrio prio(k_steps);
-    POMDP_FUSED_STEP_LOOP(prio, s) {
+    POMDP_FUSED_STEP_LOOP(prio, s, cx.stretch) {
         const RngKey key = cx.key(key0, s);
         uint32_t a_next[4];
         cx.pol.begin(s, a_next);

@@ -79,36 +79,69 @@ __device__ __forceinline__ uint4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_
 // products of the fixed words are the thread's for the whole launch (PhiloxFixed, computed before the loop), the products of
 // the call counter are wave-uniform — scalar multiplies and scalar xors — and the two xors that mix the two kinds leave the
 // vector unit eight rounds of work.  The generic form on the vector unit: about six more vector instructions per block.
+//
+// Round 3's product of word 0 does not depend on the counter's LOW word at all.  With the round function p0 = M0 c0, p1 = M1 c2,
+// c0' = hi(p1) ^ c1 ^ k0, c1' = lo(p1), c2' = hi(p0) ^ c3 ^ k1, c3' = lo(p0), and every word classed as thread-fixed for the
+// launch (F: c0, c3), wave-uniform and changing per step (V: c1 = t lo) or wave-uniform and constant (C: c2 = t hi, the key):
+//   after round 1 the words are (V, C, F, F);
+//   after round 2 they are (F, F, vector, V): the new word 0 is d_hi ^ lo(M1 c2) ^ (k0 + 0x9E3779B9) — F ^ C ^ C;
+// so round 3's M0 x0 is the same 64-bit number in every step that has the same t hi: philox_hoist computes it in front of the
+// loop, and round 3 keeps one vector multiply.  A launch's counter crosses a multiple of 2^32 at most once; the step loops run
+// as stretches that end there (stretch_end) and derive the product again at the head of each.
 struct PhiloxFixed {
     uint32_t a_lo;           // lo(M0 c0): counter word 3 after round 1
     uint32_t d_hi, d_lo;     // M1 (hi(M0 c0) ^ c3 ^ k1): round 2's product of counter word 2
+    uint32_t q_hi, q_lo;     // M0 (d_hi ^ lo(M1 c2) ^ (k0 + 0x9E3779B9)): round 3's product of word 0, for ONE c2 (philox_hoist)
 };
 __device__ __forceinline__ PhiloxFixed philox_fixed(uint32_t c0, uint32_t c3, uint32_t k1)
 {
     const uint64_t a = (uint64_t)0xD2511F53u * c0;
     const uint64_t d = (uint64_t)0xCD9E8D57u * ((uint32_t)(a >> 32) ^ c3 ^ k1);
-    return PhiloxFixed{(uint32_t)a, (uint32_t)(d >> 32), (uint32_t)d};
+    return PhiloxFixed{(uint32_t)a, (uint32_t)(d >> 32), (uint32_t)d, 0u, 0u};
 }
-// philox4x32_10(c0, c1, c2, c3, k0, k1) for the c0, c3 that `f` was made from; c1, c2, k0, k1 wave-uniform
-__device__ __forceinline__ uint4 philox4x32_10_fixed(const PhiloxFixed &f, uint32_t c1, uint32_t c2, uint32_t k0, uint32_t k1)
+// ... its round-3 product for the counter's high word c2: valid for the steps whose call counter has that high word
+__device__ __forceinline__ void philox_hoist(PhiloxFixed &f, uint32_t c2, uint32_t k0)
 {
+    const uint32_t x0 = f.d_hi ^ ((0xCD9E8D57u * c2) ^ (k0 + 0x9E3779B9u));      // (the two scalars first: one vector xor)
+    const uint64_t q = (uint64_t)0xD2511F53u * x0;
+    f.q_hi = (uint32_t)(q >> 32); f.q_lo = (uint32_t)q;
+}
+// The step at which a stretch of a step loop that starts at step s (call counter low word t_lo there) and may run to `end` has
+// to end: where the counter's low word becomes 0 — the first step with another high word — or `end`.  UNIT = 2: a loop unrolled
+// by two that keeps one product per parity; t_lo is then the parity's counter at its first step of the stretch, and the stretch
+// ends at the even step from which that parity's next step has another high word.
+template <int UNIT = 1>
+__device__ __forceinline__ int stretch_end(int s, int end, uint32_t t_lo)
+{
+    uint32_t more = 0u - t_lo - 1u;                          // further steps with this high word (t_lo = 0: 2^32 - 1)
+    if (UNIT == 2) more |= 1u;
+    const uint32_t room = (uint32_t)(end - s - 1);
+    return s + 1 + (int)(room < more ? room : more);
+}
+// philox4x32_10(c0, c1, c2, c3, k0, k1) for the c0, c3 that `f` was made from and the c2, k0 its product was hoisted for; c1,
+// c2, k0, k1 wave-uniform.  HOIST = false: the product is computed here, in every step — the loops whose registers have no
+// room for it (two more per block across the step loop).
+template <bool HOIST = true>
+__device__ __forceinline__ uint4 philox4x32_10_fixed(const PhiloxFixed &fixed, uint32_t c1, uint32_t c2, uint32_t k0, uint32_t k1)
+{
+    PhiloxFixed f = fixed;
+    if (!HOIST) philox_hoist(f, c2, k0);
     // round 1: the call counter's product (scalar)
     const uint64_t b = (uint64_t)0xCD9E8D57u * c2;
     const uint32_t u0 = (uint32_t)(b >> 32) ^ c1 ^ k0;
-    // round 2: the product of the uniform word 0 (scalar); each new word xors one thread word with one scalar
+    // round 2: the product of the uniform word 0 (scalar); the new word 0 went into the hoisted product
     const uint64_t c = (uint64_t)0xD2511F53u * u0;
     k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    uint32_t x0 = f.d_hi ^ ((uint32_t)b ^ k0);
+    uint32_t x0;
     uint32_t x2 = f.a_lo ^ ((uint32_t)(c >> 32) ^ k1);
     uint32_t x1 = f.d_lo, x3 = (uint32_t)c;
     k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    // round 3: word 3 is still uniform — its xor with the key word first
+    // round 3: word 0's product is the hoisted one; word 3 is still uniform — its xor with the key word first
     {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * x0;
         const uint64_t p1 = (uint64_t)0xCD9E8D57u * x2;
         const uint32_t n0 = __builtin_amdgcn_bitop3_b32((uint32_t)(p1 >> 32), x1, k0, 0x96);
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ (x3 ^ k1);
-        x1 = (uint32_t)p1; x3 = (uint32_t)p0; x0 = n0; x2 = n2;
+        const uint32_t n2 = f.q_hi ^ (x3 ^ k1);
+        x1 = (uint32_t)p1; x3 = f.q_lo; x0 = n0; x2 = n2;
         k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
     }
 #pragma unroll

@@ -92,24 +92,35 @@ struct NoColumn {            // the same interface for a loop that is not tape-d
 
 // quad-per-thread loops: l0 = the thread's first lane within the shard, glane0 its global id.  begin(s, a_next) at the top of
 // step s, end(s, a_next) after the step's stores: between them a_next holds the actions of step s + 1 (Synthetic) or nothing yet.
-struct SyntheticQuad {
+template <bool HOIST>        // HOIST: round 3's product of the policy's block is kept per stretch of the step loop (philox.hip.h)
+struct SyntheticQuadT {
     static constexpr bool TAPE = false;
     uint32_t glane0, n_act, k0, k1;
     uint64_t ta0;
     PhiloxFixed fx;          // the quad's block of stream ACTION: its counter words 0 and 3 are the launch's (philox4x32_10_fixed)
     // (the policy shares the env's Philox key in every launch that takes these loops: the key words are the ENV key's, so that
     // the compiler keeps one copy of them in scalar registers — a second copy made Network's loop spill scalars)
-    __device__ __forceinline__ SyntheticQuad(const TapeRef &, uint32_t, uint32_t glane0_, const RngKey &key0, const RngKey &akey0, uint32_t n_act_, int)
+    __device__ __forceinline__ SyntheticQuadT(const TapeRef &, uint32_t, uint32_t glane0_, const RngKey &key0, const RngKey &akey0, uint32_t n_act_, int)
         : glane0(glane0_), n_act(n_act_), k0(key0.k0), k1(key0.k1), ta0(((uint64_t)akey0.t_hi << 32) | akey0.t_lo),
           fx(philox_fixed(glane0_ >> 2, (uint32_t)POMDP_STREAM_ACTION << 24, key0.k1)) {}
-    __device__ __forceinline__ uint4 block(uint64_t ta) const
+    // a stretch of the step loop from step s: the product for its counter's high word; it ends at `end` or where that word changes
+    __device__ __forceinline__ int stretch(int s, int end)
     {
-        return philox4x32_10_fixed(fx, (uint32_t)ta, (uint32_t)(ta >> 32), k0, k1);
+        if constexpr (!HOIST) return end;
+        const uint64_t ta = ta0 + (uint64_t)s;
+        philox_hoist(fx, (uint32_t)(ta >> 32), k0);
+        return stretch_end(s, end, (uint32_t)ta);
     }
-    // the actions of the call counter BEFORE akey0's: what pomdp_synthetic_actions would have written for the launch's first step
+    __device__ __forceinline__ uint4 block(uint64_t ta) const   // HOIST: inside the stretch `fx` was hoisted for
+    {
+        return philox4x32_10_fixed<HOIST>(fx, (uint32_t)ta, (uint32_t)(ta >> 32), k0, k1);
+    }
+    // the actions of the call counter BEFORE akey0's: what pomdp_synthetic_actions would have written for the launch's first step.
+    // Once per launch, and its counter's high word is not the first stretch's when ta0's low word is 0: the product is its own.
     __device__ __forceinline__ u32x4 first() const
     {
-        const uint4 w = block(ta0 - 1ull);
+        const uint64_t ta = ta0 - 1ull;
+        const uint4 w = philox4x32_10_fixed<false>(fx, (uint32_t)ta, (uint32_t)(ta >> 32), k0, k1);
         return u32x4{__umulhi(w.x, n_act), __umulhi(w.y, n_act), __umulhi(w.z, n_act), __umulhi(w.w, n_act)};
     }
     __device__ __forceinline__ void begin(int s, uint32_t (&a)[4]) const
@@ -120,6 +131,8 @@ struct SyntheticQuad {
     __device__ __forceinline__ void end(int, uint32_t (&)[4]) const {}
     __device__ __forceinline__ void count_bad(uint32_t) const {}
 };
+struct SyntheticQuad : SyntheticQuadT<true> { using SyntheticQuadT<true>::SyntheticQuadT; };
+struct SyntheticQuadPlain : SyntheticQuadT<false> { using SyntheticQuadT<false>::SyntheticQuadT; };   // for the loops without room for the product
 struct TapeQuad {
     static constexpr bool TAPE = true;
     TapeColumn<uint32_t> col;
@@ -139,6 +152,7 @@ struct TapeQuad {
     __device__ __forceinline__ void begin(int s, uint32_t (&a)[4]) { col.request(s); a[0] = a[1] = a[2] = a[3] = 0; }
     __device__ __forceinline__ void end(int, uint32_t (&a)[4]) const { unpack(col.nxt, a); }
     __device__ __forceinline__ void count_bad(uint32_t n_bad) const { if (n_bad && err) atomicAdd(err, n_bad); }
+    __device__ __forceinline__ int stretch(int, int end) const { return end; }   // nothing hoisted
 };
 
 // The same tape read TWO steps ahead, for a loop unrolled by two (steps_quad_kernel): row r lives in register r & 1; the top
@@ -166,6 +180,7 @@ struct TapeQuadAhead {
     }
     template <int PAR> __device__ __forceinline__ void end_par(int, uint32_t (&a)[4]) const { TapeQuad::unpack(PAR == 0 ? odd : even, a); }
     __device__ __forceinline__ void count_bad(uint32_t n_bad) const { if (n_bad && err) atomicAdd(err, n_bad); }
+    __device__ __forceinline__ int stretch(int, int end) const { return end; }   // nothing hoisted
 };
 
 // ---- two lanes per thread: half a quad (BattleShip's small shards, fused_impl.hip.h) ----------------------------------------
@@ -215,6 +230,7 @@ struct SyntheticPair {
     }
     __device__ __forceinline__ void end(int, uint32_t (&)[2]) const {}
     __device__ __forceinline__ void count_bad(uint32_t) const {}
+    __device__ __forceinline__ int stretch(int, int end) const { return end; }   // nothing hoisted
 };
 struct TapePair {
     static constexpr bool TAPE = true;
@@ -226,10 +242,12 @@ struct TapePair {
     __device__ __forceinline__ void begin(int s, uint32_t (&a)[2]) { col.request(s); a[0] = a[1] = 0; }
     __device__ __forceinline__ void end(int, uint32_t (&a)[2]) const { a[0] = col.nxt & 0xFFu; a[1] = (uint32_t)col.nxt >> 8; }
     __device__ __forceinline__ void count_bad(uint32_t n_bad) const { if (n_bad && err) atomicAdd(err, n_bad); }
+    __device__ __forceinline__ int stretch(int, int end) const { return end; }   // nothing hoisted
 };
-template <class Pol, int LPT> struct lanes_policy { using type = Pol; };
-template <> struct lanes_policy<SyntheticQuad, 2> { using type = SyntheticPair; };
-template <> struct lanes_policy<TapeQuad, 2> { using type = TapePair; };
+template <class Pol, int LPT, bool HOIST = true> struct lanes_policy { using type = Pol; };
+template <bool HOIST> struct lanes_policy<SyntheticQuad, 2, HOIST> { using type = SyntheticPair; };
+template <bool HOIST> struct lanes_policy<TapeQuad, 2, HOIST> { using type = TapePair; };
+template <> struct lanes_policy<SyntheticQuad, 4, false> { using type = SyntheticQuadPlain; };
 
 // ---- a thread that owns a quad of consecutive lanes (the quad-per-thread loops) ------------------------------------
 // l0: the thread's first lane within the shard (a multiple of 4).  first(): the actions of the launch's first step.
