@@ -34,98 +34,50 @@ __global__ __launch_bounds__(BLOCK) void reset_where_kernel(const typename Env::
 }
 
 // ---- the returns sink of a frozen-lane loop ---------------------------------------------------------------------------------
-// The statistics of pomdp_return_stats, LPT lanes per thread at `idx[j]` within the shard.  A live step adds its reward (the
-// reference's float64 value, from the workgroup's table of the env's reward codes) and banks the return when it ends the
-// episode — returns_step, as pomdp_collect_returns does — and counts one step; a frozen lane adds nothing.  `steps` is kept
-// in a register and stored once, like the rest.
+// The statistics of pomdp_return_stats, LPT lanes per thread, in ReturnsRegs (traj_out.hip.h).  A live step adds its reward and
+// banks the return when it ends the episode — as pomdp_collect_returns does — and counts one step; a frozen lane adds
+// nothing.  What is this sink's own: `steps` is kept in a register and stored once, like the rest.
 template <class Env, int LPT>
 struct EpisodeReturns {
-    static constexpr bool BANK = !never_done<Env>::value;
-    double *acc;
-    uint32_t *cnt;
-    int64_t pitch;
-    double discount;
-    double ret[LPT], disc[LPT], ret_done[LPT], ret_sum[LPT];
-    uint32_t episodes[LPT], steps[LPT];
-    __device__ __forceinline__ EpisodeReturns(double *acc_, uint32_t *cnt_, double discount_, int64_t pitch_)
-        : acc(acc_), cnt(cnt_), pitch(pitch_), discount(discount_)
-    {
-        reward_f64_lds<Env>()[threadIdx.x & 255u] = Env::code_reward(threadIdx.x & 255u);
-    }
+    ReturnsRegs<Env, LPT> regs;
+    uint32_t steps[LPT];
+    __device__ __forceinline__ EpisodeReturns(double *acc, uint32_t *cnt, uint64_t discount_bits, int64_t pitch)
+        : regs(acc, cnt, discount_bits, pitch) {}
     __device__ __forceinline__ void begin(int j, uint32_t i)
     {
-        ret[j] = ld_stream(acc + i); disc[j] = ld_stream(acc + pitch + i);
-        ret_done[j] = 0.0; ret_sum[j] = 0.0; episodes[j] = 0;
-        if constexpr (BANK) {
-            ret_done[j] = ld_stream(acc + 2 * pitch + i); ret_sum[j] = ld_stream(acc + 3 * pitch + i);
-            episodes[j] = ld_stream(cnt + i);
-        }
-        steps[j] = ld_stream(cnt + pitch + i);
+        regs.load_lane(j, i);
+        steps[j] = ld_stream(regs.cnt_w + regs.pitch + i);
     }
     // the same for a quad of consecutive lanes l0 .. l0 + 3 (LPT = 4, rows on 16-byte boundaries): 16-byte accesses — four
     // scalar 8-byte streamed accesses per row and quad cost the quad loop's first 16-step launch a third of its time
     __device__ __forceinline__ void begin4(uint32_t l0)
     {
         static_assert(LPT == 4, "a quad per thread");
-        auto row = [&](int q, double (&v)[LPT]) {
-            const f64x2 *r = reinterpret_cast<const f64x2 *>(acc + q * pitch + l0);
-            const f64x2 lo = __builtin_nontemporal_load(r), hi = __builtin_nontemporal_load(r + 1);
-            v[0] = lo[0]; v[1] = lo[1]; v[2] = hi[0]; v[3] = hi[1];
-        };
-        row(0, ret); row(1, disc);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { ret_done[j] = 0.0; ret_sum[j] = 0.0; episodes[j] = 0; }
-        if constexpr (BANK) {
-            row(2, ret_done); row(3, ret_sum);
-            const u32x4 e = ld_stream4(cnt + l0);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) episodes[j] = e[j];
-        }
-        const u32x4 n = ld_stream4(cnt + pitch + l0);
+        regs.load_row(l0);
+        const u32x4 n = ld_stream4(regs.cnt_w + regs.pitch + l0);
 #pragma unroll
         for (int j = 0; j < 4; ++j) steps[j] = n[j];
     }
     __device__ __forceinline__ void finish4(uint32_t l0)
     {
         static_assert(LPT == 4, "a quad per thread");
-        auto row = [&](int q, const double (&v)[LPT]) {
-            f64x2 *r = reinterpret_cast<f64x2 *>(acc + q * pitch + l0);
-            __builtin_nontemporal_store(f64x2{v[0], v[1]}, r);
-            __builtin_nontemporal_store(f64x2{v[2], v[3]}, r + 1);
-        };
-        row(0, ret); row(1, disc);
-        if constexpr (BANK) {
-            row(2, ret_done); row(3, ret_sum);
-            st_stream4(cnt + l0, episodes[0], episodes[1], episodes[2], episodes[3]);
-        }
-        st_stream4(cnt + pitch + l0, steps[0], steps[1], steps[2], steps[3]);
+        regs.store_row(l0);
+        st_stream4(regs.cnt_w + regs.pitch + l0, steps[0], steps[1], steps[2], steps[3]);
     }
     // `record`: the step's packed record (action | ob << 8 | reward code << 16 | done << 24)
     __device__ __forceinline__ void put(int j, uint32_t record, bool live)
     {
         if (live) {
-            returns_step<Env>(ret[j], disc[j], ret_sum[j], episodes[j], ret_done[j], discount, record >> 16,
-                              BANK ? mask_of_bit(record, 24) : 0u);
+            regs.step_record(j, record);
             ++steps[j];
         }
     }
     __device__ __forceinline__ void finish(int j, uint32_t i)
     {
-        st_stream(acc + i, ret[j]); st_stream(acc + pitch + i, disc[j]);
-        if constexpr (BANK) {
-            st_stream(acc + 2 * pitch + i, ret_done[j]); st_stream(acc + 3 * pitch + i, ret_sum[j]);
-            st_stream(cnt + i, episodes[j]);
-        }
-        st_stream(cnt + pitch + i, steps[j]);
+        regs.store_lane(j, i);
+        st_stream(regs.cnt_w + regs.pitch + i, steps[j]);
     }
 };
-
-static __device__ __forceinline__ double bits_f64(uint64_t b)
-{
-    double d;
-    __builtin_memcpy(&d, &b, 8);
-    return d;
-}
 
 // ---- the general frozen-lane loop: one lane per thread, any n, every env ----------------------------------------------------
 // k_steps consecutive pomdp_<env>_step(flags = 0) calls at t0 + s with the synthetic policy's actions of t0 + s (TAPE: row s of
@@ -156,7 +108,7 @@ __global__ __launch_bounds__(BLOCK) void episodes_kernel(uint32_t *__restrict__ 
     bool frozen = !in_range || ld_stream(done + wg0 + rc) != 0;
     using Out = typename std::conditional<RETS, EpisodeReturns<Env, 1>, LaneOut<L, typename Env::Reward, 1>>::type;
     Out out = [&]() {
-        if constexpr (RETS) return Out(reinterpret_cast<double *>(out0) + wg0, reinterpret_cast<uint32_t *>(out1) + wg0, bits_f64(discount_bits), rec);
+        if constexpr (RETS) return Out(reinterpret_cast<double *>(out0) + wg0, reinterpret_cast<uint32_t *>(out1) + wg0, discount_bits, rec);
         else return Out(out0, nullptr, nullptr, nullptr, rec, wg0);
     }();
     if constexpr (RETS) out.begin(0, rc);
@@ -237,7 +189,7 @@ __global__ __launch_bounds__(BLOCK) void episodes_quad_kernel(uint32_t *__restri
     typename lanes_policy<Pol, 4, false>::type pol(tape, l0, glane0, key0, key0, n_act, k_steps);
     using Out = typename std::conditional<RETS, EpisodeReturns<Env, 4>, QuadOut<L>>::type;
     Out out = [&]() {
-        if constexpr (RETS) return Out(reinterpret_cast<double *>(out0), reinterpret_cast<uint32_t *>(out1), bits_f64(discount_bits), rec);
+        if constexpr (RETS) return Out(reinterpret_cast<double *>(out0), reinterpret_cast<uint32_t *>(out1), discount_bits, rec);
         else return Out(out0, nullptr, nullptr, nullptr, rec, l0);
     }();
     typename Env::State st[4];

@@ -22,7 +22,8 @@
 //            v_perm_b32) and stores four bytes per plane: four 256-byte pieces per wave-step instead of one 1 KB piece.
 //   Returns  no trajectory at all: the reduction the reference's callers apply to the stream — r += discount * rw; discount
 //            *= .95 per step, one return per episode (network.py:175-191, rock.py:553-575) — kept per lane in registers
-//            across the launch and written once when it ends (include/pomdp_hip.h: pomdp_collect_returns).
+//            across the launch and written once when it ends (include/pomdp_hip.h: pomdp_collect_returns).  One register
+//            accumulator, ReturnsRegs, behind the quad / pair / lane sinks here and the frozen-lane loops' (episodes.hip).
 //
 // Blocked, Packed and Narrow rows hold the action TAKEN at step s (row s of every field belongs to step s); they have no row
 // of "next actions" — a launch derives its first actions from the synthetic policy itself (they are a function of (seed,
@@ -255,6 +256,19 @@ template <> struct lanes_policy<SyntheticQuad, 4, false> { using type = Syntheti
 // counter, o / r (raw 32-bit patterns) / rc (reward codes, read by Packed only) / d (0 or 1) — then on to the next row.
 template <class L> struct QuadOut;
 
+// put()'s arguments from the lanes' packed records (a lane step that produces the record directly: RockEnv::step_rec), for the
+// 13-byte sinks' put_records; valid for the envs whose reward code is the int8 reward itself
+static __device__ __forceinline__ void unpack_records(const uint32_t (&rec)[4], uint32_t (&a)[4], uint32_t (&o)[4], uint32_t (&r)[4], uint32_t (&d)[4])
+{
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        a[j] = rec[j] & 0xFFu;
+        o[j] = __builtin_amdgcn_ubfe(rec[j], 8u, 8u);
+        r[j] = (uint32_t)__builtin_amdgcn_sbfe(rec[j], 16u, 8u);
+        d[j] = rec[j] >> 24;
+    }
+}
+
 template <bool ACT> struct QuadOut<ColumnsT<ACT>> {
     uint32_t *action_w, *ob_w, *reward_w, *done_w;
     int64_t rec;
@@ -285,18 +299,10 @@ template <bool ACT> struct QuadOut<ColumnsT<ACT>> {
         st_stream(done_w, d[0] | (d[1] << 8) | (d[2] << 16) | (d[3] << 24));
         action_w += rec; ob_w += rec; reward_w += rec; done_w += rec / 4;
     }
-    // the same from the lanes' packed records (a lane step that produces the record directly: RockEnv::step_rec) — unpacked
-    // here; valid for the envs whose reward code is the int8 reward itself
     __device__ __forceinline__ void put_records(const uint32_t (&rec)[4], const uint32_t (&a_next)[4])
     {
         uint32_t a[4], o[4], r[4], d[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            a[j] = rec[j] & 0xFFu;
-            o[j] = __builtin_amdgcn_ubfe(rec[j], 8u, 8u);
-            r[j] = (uint32_t)__builtin_amdgcn_sbfe(rec[j], 16u, 8u);
-            d[j] = rec[j] >> 24;
-        }
+        unpack_records(rec, a, o, r, d);
         put(a, a_next, o, r, r, d);
     }
     __device__ __forceinline__ void finish(int) {}
@@ -319,18 +325,10 @@ template <> struct QuadOut<Blocked> {
         st_stream(reinterpret_cast<uint32_t *>(wd), d[0] | (d[1] << 8) | (d[2] << 16) | (d[3] << 24));
         w += row_bytes; wd += row_bytes;
     }
-    // the same from the lanes' packed records (a lane step that produces the record directly: RockEnv::step_rec) — unpacked
-    // here; valid for the envs whose reward code is the int8 reward itself
     __device__ __forceinline__ void put_records(const uint32_t (&rec)[4], const uint32_t (&a_next)[4])
     {
         uint32_t a[4], o[4], r[4], d[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            a[j] = rec[j] & 0xFFu;
-            o[j] = __builtin_amdgcn_ubfe(rec[j], 8u, 8u);
-            r[j] = (uint32_t)__builtin_amdgcn_sbfe(rec[j], 16u, 8u);
-            d[j] = rec[j] >> 24;
-        }
+        unpack_records(rec, a, o, r, d);
         put(a, a_next, o, r, r, d);
     }
     __device__ __forceinline__ void finish(int) {}
@@ -388,8 +386,8 @@ template <> struct QuadOut<Narrow> {
 };
 
 // The workgroup's table of the rewards its env's codes stand for, as the float64 values the reference's callers add up
-// (Env::code_reward).  Filled by the sinks' constructors — every fused loop constructs its sink before the barrier that
-// follows its table staging, and reads it only inside the step loop.
+// (Env::code_reward).  Filled by ReturnsRegs' constructor — every fused loop constructs its sink, and with it the accumulator,
+// before the barrier that follows its table staging, and reads the table only inside the step loop.
 template <class Env>
 static __device__ __forceinline__ double (&reward_f64_lds())[256]
 {
@@ -453,67 +451,126 @@ static __device__ __forceinline__ void returns_step(double &ret, double &disc, d
     }
 }
 
-template <class Env> struct QuadOut<Returns<Env>> {
+// The statistics of N lanes of one thread in registers, behind every returns sink: the quad / pair sinks below, LaneOut's and
+// the frozen-lane loops' (episodes.hip).  acc: double [4][pitch] = ret | disc | ret_done | ret_sum, cnt: uint32 [2][pitch] =
+// episodes | steps (include/pomdp_hip.h: pomdp_return_stats); an env that never ends an episode (BANK false) neither reads
+// nor writes ret_done, ret_sum and episodes.  `steps` is the sink's own business.  Addresses are formed as base + row +
+// index in exactly that order: a sink that wants its lane offset added first puts it into the base.
+template <class Env, int N> struct ReturnsRegs {
     static constexpr bool BANK = !never_done<Env>::value;
+    typedef uint32_t u32xN __attribute__((ext_vector_type(N)));
     double *acc_w;
     uint32_t *cnt_w;
     int64_t pitch;
     double discount;
-    double ret[4], disc[4], ret_done[4], ret_sum[4];
-    uint32_t episodes[4];
-    // acc: double [4][pitch], cnt: int32 [2][pitch] (include/pomdp_hip.h: pomdp_return_stats); the discount rides in the slot
-    // of the reward pointer as its bit pattern (the kernels' signatures are the trajectory sinks')
-    __device__ __forceinline__ QuadOut(void *acc, void *cnt, void *discount_bits, void *, int64_t pitch_, uint32_t l0)
-        : acc_w(reinterpret_cast<double *>(acc) + l0), cnt_w(reinterpret_cast<uint32_t *>(cnt) + l0), pitch(pitch_)
+    double ret[N], disc[N], ret_done[N], ret_sum[N];
+    uint32_t episodes[N];
+    // also fills the workgroup's slot of the reward table (reward_f64_lds: constructed before the staging barrier)
+    __device__ __forceinline__ ReturnsRegs(double *acc, uint32_t *cnt, uint64_t discount_bits, int64_t pitch_)
+        : acc_w(acc), cnt_w(cnt), pitch(pitch_)
     {
-        const uint64_t bits = reinterpret_cast<uint64_t>(discount_bits);
-        __builtin_memcpy(&discount, &bits, 8);
+        __builtin_memcpy(&discount, &discount_bits, 8);
         reward_f64_lds<Env>()[threadIdx.x & 255u] = Env::code_reward(threadIdx.x & 255u);
-        auto row = [&](int q, double (&v)[4]) {
-            const f64x2 lo = __builtin_nontemporal_load(reinterpret_cast<const f64x2 *>(acc_w + q * pitch));
-            const f64x2 hi = __builtin_nontemporal_load(reinterpret_cast<const f64x2 *>(acc_w + q * pitch) + 1);
-            v[0] = lo[0]; v[1] = lo[1]; v[2] = hi[0]; v[3] = hi[1];
+    }
+    // lane j of the thread = lane i of the rows: scalar streamed accesses
+    __device__ __forceinline__ void load_lane(int j, uint32_t i)
+    {
+        ret[j] = ld_stream(acc_w + i); disc[j] = ld_stream(acc_w + pitch + i);
+        if constexpr (BANK) {
+            ret_done[j] = ld_stream(acc_w + 2 * pitch + i); ret_sum[j] = ld_stream(acc_w + 3 * pitch + i);
+            episodes[j] = ld_stream(cnt_w + i);
+        }
+    }
+    __device__ __forceinline__ void store_lane(int j, uint32_t i)
+    {
+        st_stream(acc_w + i, ret[j]); st_stream(acc_w + pitch + i, disc[j]);
+        if constexpr (BANK) {
+            st_stream(acc_w + 2 * pitch + i, ret_done[j]); st_stream(acc_w + 3 * pitch + i, ret_sum[j]);
+            st_stream(cnt_w + i, episodes[j]);
+        }
+    }
+    // the thread's N lanes = lanes l0 .. l0 + N - 1 of the rows (N = 2, 4; rows on 16-byte boundaries): the double rows 16
+    // bytes at a time, the episode counts as one access of N words
+    __device__ __forceinline__ void load_row(uint32_t l0)
+    {
+        auto row = [&](int q, double (&v)[N]) {
+            const f64x2 *r = reinterpret_cast<const f64x2 *>(acc_w + q * pitch + l0);
+#pragma unroll
+            for (int h = 0; h < N / 2; ++h) {
+                const f64x2 x = __builtin_nontemporal_load(r + h);
+                v[2 * h] = x[0]; v[2 * h + 1] = x[1];
+            }
         };
         row(0, ret); row(1, disc);
         if constexpr (BANK) {
             row(2, ret_done); row(3, ret_sum);
-            const u32x4 e = ld_stream4(cnt_w);
-            episodes[0] = e[0]; episodes[1] = e[1]; episodes[2] = e[2]; episodes[3] = e[3];
+            const u32xN e = __builtin_nontemporal_load(reinterpret_cast<const u32xN *>(cnt_w + l0));
+#pragma unroll
+            for (int j = 0; j < N; ++j) episodes[j] = e[j];
         }
     }
-    template <class Pol> __device__ __forceinline__ u32x4 first(const Pol &pol, int) { return pol.first(); }
-    __device__ __forceinline__ void put_records(const uint32_t (&r)[4], const uint32_t (&)[4])
+    __device__ __forceinline__ void store_row(uint32_t l0)
     {
+        auto row = [&](int q, const double (&v)[N]) {
+            f64x2 *r = reinterpret_cast<f64x2 *>(acc_w + q * pitch + l0);
 #pragma unroll
-        for (int j = 0; j < 4; ++j)                           // the done byte of a record is 0 or 1
-            returns_step<Env>(ret[j], disc[j], ret_sum[j], episodes[j], ret_done[j], discount, r[j] >> 16, mask_of_bit(r[j], 24));
-    }
-    __device__ __forceinline__ void put(const uint32_t (&)[4], const uint32_t (&)[4], const uint32_t (&)[4],
-                                        const uint32_t (&)[4], const uint32_t (&rc)[4], const uint32_t (&d)[4])
-    {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            returns_step<Env>(ret[j], disc[j], ret_sum[j], episodes[j], ret_done[j], discount, rc[j], BANK ? mask_of_bit(d[j], 0) : 0u);
-    }
-    __device__ __forceinline__ void finish(int k_steps)
-    {
-        auto row = [&](int q, const double (&v)[4]) {
-            __builtin_nontemporal_store(f64x2{v[0], v[1]}, reinterpret_cast<f64x2 *>(acc_w + q * pitch));
-            __builtin_nontemporal_store(f64x2{v[2], v[3]}, reinterpret_cast<f64x2 *>(acc_w + q * pitch) + 1);
+            for (int h = 0; h < N / 2; ++h) __builtin_nontemporal_store(f64x2{v[2 * h], v[2 * h + 1]}, r + h);
         };
         row(0, ret); row(1, disc);
         if constexpr (BANK) {
             row(2, ret_done); row(3, ret_sum);
-            st_stream4(cnt_w, episodes[0], episodes[1], episodes[2], episodes[3]);
-        }
+            u32xN e;
 #pragma unroll
-        for (int j = 0; j < 4; ++j)                          // steps += k: no value comes back, nothing to wait for
-            (void)__hip_atomic_fetch_add(cnt_w + pitch + j, (uint32_t)k_steps, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            for (int j = 0; j < N; ++j) e[j] = episodes[j];
+            __builtin_nontemporal_store(e, reinterpret_cast<u32xN *>(cnt_w + l0));
+        }
+    }
+    // one step of lane j, from its packed record (whose done byte is 0 or 1) or from its reward code and done flag (0 or 1)
+    __device__ __forceinline__ void step_record(int j, uint32_t record)
+    {
+        returns_step<Env>(ret[j], disc[j], ret_sum[j], episodes[j], ret_done[j], discount, record >> 16, BANK ? mask_of_bit(record, 24) : 0u);
+    }
+    __device__ __forceinline__ void step_done(int j, uint32_t rcode, uint32_t d)
+    {
+        returns_step<Env>(ret[j], disc[j], ret_sum[j], episodes[j], ret_done[j], discount, rcode, BANK ? mask_of_bit(d, 0) : 0u);
     }
 };
 
+// The returns sink of a thread that owns N consecutive lanes from l0 (QuadOut: 4, PairOut: 2): the rows are read when the sink
+// is constructed and written by finish(), which also adds the launch's steps.  The discount rides in the slot of the reward
+// pointer as its bit pattern (the kernels' signatures are the trajectory sinks').
+template <class Env, int N> struct ReturnsRowOut {
+    ReturnsRegs<Env, N> regs;
+    __device__ __forceinline__ ReturnsRowOut(void *acc, void *cnt, void *discount_bits, void *, int64_t pitch_, uint32_t l0)
+        : regs(reinterpret_cast<double *>(acc) + l0, reinterpret_cast<uint32_t *>(cnt) + l0, reinterpret_cast<uint64_t>(discount_bits), pitch_)
+    {
+        regs.load_row(0);
+    }
+    template <class Pol> __device__ __forceinline__ u32x4 first(const Pol &pol, int) { return pol.first(); }
+    __device__ __forceinline__ void put_records(const uint32_t (&r)[N], const uint32_t (&)[N])
+    {
+#pragma unroll
+        for (int j = 0; j < N; ++j) regs.step_record(j, r[j]);
+    }
+    __device__ __forceinline__ void put(const uint32_t (&)[N], const uint32_t (&)[N], const uint32_t (&)[N],
+                                        const uint32_t (&)[N], const uint32_t (&rc)[N], const uint32_t (&d)[N])
+    {
+#pragma unroll
+        for (int j = 0; j < N; ++j) regs.step_done(j, rc[j], d[j]);
+    }
+    __device__ __forceinline__ void finish(int k_steps)
+    {
+        regs.store_row(0);
+#pragma unroll
+        for (int j = 0; j < N; ++j)                          // steps += k: no value comes back, nothing to wait for
+            (void)__hip_atomic_fetch_add(regs.cnt_w + regs.pitch + j, (uint32_t)k_steps, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+};
+template <class Env> struct QuadOut<Returns<Env>> : ReturnsRowOut<Env, 4> { using ReturnsRowOut<Env, 4>::ReturnsRowOut; };
+
 // ---- a thread that owns TWO consecutive lanes: the 4-byte sinks and the returns sink (the 13-byte layouts are bound by their
-// store stream whatever the geometry: they keep the quad-per-thread loops).  put(): as QuadOut's, two lanes wide.
+// store stream whatever the geometry: they keep the quad-per-thread loops).  put(): as QuadOut's, two lanes wide.  The returns
+// sink is ReturnsRowOut<Env, 2>, the body it shares with QuadOut's.
 template <class L> struct PairOut;
 template <> struct PairOut<Packed> {
     uint32_t *w;
@@ -557,57 +614,7 @@ template <> struct PairOut<Narrow> {
     }
     __device__ __forceinline__ void finish(int) {}
 };
-template <class Env> struct PairOut<Returns<Env>> {
-    static constexpr bool BANK = !never_done<Env>::value;
-    double *acc_w;
-    uint32_t *cnt_w;
-    int64_t pitch;
-    double discount;
-    double ret[2], disc[2], ret_done[2], ret_sum[2];
-    uint32_t episodes[2];
-    __device__ __forceinline__ PairOut(void *acc, void *cnt, void *discount_bits, void *, int64_t pitch_, uint32_t l0)
-        : acc_w(reinterpret_cast<double *>(acc) + l0), cnt_w(reinterpret_cast<uint32_t *>(cnt) + l0), pitch(pitch_)
-    {
-        const uint64_t bits = reinterpret_cast<uint64_t>(discount_bits);
-        __builtin_memcpy(&discount, &bits, 8);
-        reward_f64_lds<Env>()[threadIdx.x & 255u] = Env::code_reward(threadIdx.x & 255u);
-        auto row = [&](int q, double (&v)[2]) {
-            const f64x2 x = __builtin_nontemporal_load(reinterpret_cast<const f64x2 *>(acc_w + q * pitch));
-            v[0] = x[0]; v[1] = x[1];
-        };
-        row(0, ret); row(1, disc);
-        if constexpr (BANK) {
-            row(2, ret_done); row(3, ret_sum);
-            const u32x2 e = ld_stream2(cnt_w);
-            episodes[0] = e[0]; episodes[1] = e[1];
-        }
-    }
-    __device__ __forceinline__ void put(const uint32_t (&)[2], const uint32_t (&)[2], const uint32_t (&)[2], const uint32_t (&)[2],
-                                        const uint32_t (&rc)[2], const uint32_t (&d)[2])
-    {
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-            returns_step<Env>(ret[j], disc[j], ret_sum[j], episodes[j], ret_done[j], discount, rc[j], BANK ? mask_of_bit(d[j], 0) : 0u);
-    }
-    __device__ __forceinline__ void put_records(const uint32_t (&r)[2], const uint32_t (&)[2])
-    {
-#pragma unroll
-        for (int j = 0; j < 2; ++j)                           // the done byte of a record is 0 or 1
-            returns_step<Env>(ret[j], disc[j], ret_sum[j], episodes[j], ret_done[j], discount, r[j] >> 16, mask_of_bit(r[j], 24));
-    }
-    __device__ __forceinline__ void finish(int k_steps)
-    {
-        auto row = [&](int q, const double (&v)[2]) { __builtin_nontemporal_store(f64x2{v[0], v[1]}, reinterpret_cast<f64x2 *>(acc_w + q * pitch)); };
-        row(0, ret); row(1, disc);
-        if constexpr (BANK) {
-            row(2, ret_done); row(3, ret_sum);
-            st_stream2(cnt_w, episodes[0], episodes[1]);
-        }
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-            (void)__hip_atomic_fetch_add(cnt_w + pitch + j, (uint32_t)k_steps, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-};
+template <class Env> struct PairOut<Returns<Env>> : ReturnsRowOut<Env, 2> { using ReturnsRowOut<Env, 2>::ReturnsRowOut; };
 // ---- packed records through a scalar row base (steps_quad_kernel: RockSample's loops, bound by vector-instruction issue) ----
 // QuadOut<Packed> / PairOut<Packed> with the address split in two: the row pointer is wave-uniform — the workgroup's first
 // record of the row, l0 less the thread's own lanes — and the thread's byte offset within the row a 32-bit constant of the
@@ -744,50 +751,23 @@ template <class RT, int LPT> struct LaneOut<Narrow, RT, LPT> {
     __device__ __forceinline__ void finish(int, uint32_t, int) {}
 };
 
+// ReturnsRegs one lane at a time: begin() reads lane j's statistics, finish() writes them and adds the launch's steps
 template <class Env, class RT, int LPT> struct LaneOut<Returns<Env>, RT, LPT> {
-    static constexpr bool BANK = !never_done<Env>::value;
-    double *acc_w;
-    uint32_t *cnt_w;
-    int64_t pitch;
-    double discount;
-    double ret[LPT], disc[LPT], ret_done[LPT], ret_sum[LPT];
-    uint32_t episodes[LPT];
+    ReturnsRegs<Env, LPT> regs;
     __device__ __forceinline__ LaneOut(void *acc, void *cnt, void *discount_bits, void *, int64_t pitch_, uint32_t wg0)
-        : acc_w(reinterpret_cast<double *>(acc) + wg0), cnt_w(reinterpret_cast<uint32_t *>(cnt) + wg0), pitch(pitch_)
-    {
-        const uint64_t bits = reinterpret_cast<uint64_t>(discount_bits);
-        __builtin_memcpy(&discount, &bits, 8);
-        reward_f64_lds<Env>()[threadIdx.x & 255u] = Env::code_reward(threadIdx.x & 255u);
-    }
-    __device__ __forceinline__ void begin(int j, uint32_t rel)
-    {
-        ret[j] = ld_stream(acc_w + rel); disc[j] = ld_stream(acc_w + pitch + rel);
-        if constexpr (BANK) {
-            ret_done[j] = ld_stream(acc_w + 2 * pitch + rel); ret_sum[j] = ld_stream(acc_w + 3 * pitch + rel);
-            episodes[j] = ld_stream(cnt_w + rel);
-        }
-    }
+        : regs(reinterpret_cast<double *>(acc) + wg0, reinterpret_cast<uint32_t *>(cnt) + wg0, reinterpret_cast<uint64_t>(discount_bits), pitch_) {}
+    __device__ __forceinline__ void begin(int j, uint32_t rel) { regs.load_lane(j, rel); }
     __device__ __forceinline__ int load_first(uint32_t) const { return 0; }
     __device__ __forceinline__ void store_first(uint32_t, int) const {}
     __device__ __forceinline__ void first_done() {}
     __device__ __forceinline__ void put_next_action(uint32_t, int) const {}
-    __device__ __forceinline__ void put(int j, uint32_t rel, int, int, RT, uint32_t rcode, int d)
-    {
-        returns_step<Env>(ret[j], disc[j], ret_sum[j], episodes[j], ret_done[j], discount, rcode, BANK ? mask_of_bit((uint32_t)(d != 0), 0) : 0u);
-    }
-    __device__ __forceinline__ void put_record(int j, uint32_t rel, uint32_t record)
-    {
-        returns_step<Env>(ret[j], disc[j], ret_sum[j], episodes[j], ret_done[j], discount, record >> 16, mask_of_bit(record, 24));
-    }
+    __device__ __forceinline__ void put(int j, uint32_t, int, int, RT, uint32_t rcode, int d) { regs.step_done(j, rcode, (uint32_t)(d != 0)); }
+    __device__ __forceinline__ void put_record(int j, uint32_t, uint32_t record) { regs.step_record(j, record); }
     __device__ __forceinline__ void next_row() {}
     __device__ __forceinline__ void finish(int j, uint32_t rel, int k_steps)
     {
-        st_stream(acc_w + rel, ret[j]); st_stream(acc_w + pitch + rel, disc[j]);
-        if constexpr (BANK) {
-            st_stream(acc_w + 2 * pitch + rel, ret_done[j]); st_stream(acc_w + 3 * pitch + rel, ret_sum[j]);
-            st_stream(cnt_w + rel, episodes[j]);
-        }
-        (void)__hip_atomic_fetch_add(cnt_w + pitch + rel, (uint32_t)k_steps, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        regs.store_lane(j, rel);
+        (void)__hip_atomic_fetch_add(regs.cnt_w + regs.pitch + rel, (uint32_t)k_steps, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 };
 

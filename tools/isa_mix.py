@@ -49,6 +49,14 @@ ALIAS = {
 DEFAULT_COST = 4.0
 
 
+ASM_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off"]
+
+
+def compile_asm(src, out, flags=ASM_FLAGS):
+    """One translation unit to device assembly text."""
+    subprocess.check_call(["/opt/rocm/bin/hipcc"] + list(flags) + ["--cuda-device-only", "-S", "-o", out, src], stderr=subprocess.DEVNULL)
+
+
 def assembly(path=None):
     """The device assembly of the units (concatenated); `path`: a directory to keep / reuse the .s files in."""
     from concurrent.futures import ThreadPoolExecutor
@@ -60,8 +68,7 @@ def assembly(path=None):
         src = os.path.join(CSRC, u)
         if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(os.path.join(r, f)) for r, _, fs in os.walk(CSRC)
                                                                   for f in fs if f.endswith((".hip", ".h"))):
-            subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
-                                   "--cuda-device-only", "-S", "-o", out, src], stderr=subprocess.DEVNULL)
+            compile_asm(src, out)
         return open(out).read()
 
     with ThreadPoolExecutor(max_workers=len(UNITS)) as ex:
