@@ -28,6 +28,7 @@ CONFIGS = [
     ("battleship", "Battleship-v0", dict(board_size=(8, 6), max_len=4)),
     ("tiger", "Tiger-v0", {}), ("network", "Network-v0", {}), ("network", "Network-v0", dict(n_machines=16, problem_type=1)),
     ("network", "Network-v0", dict(n_machines=31, problem_type=3)),
+    ("battleship", "Battleship-v0", dict(board_size=(8, 8), max_len=4)),          # three mask words
 ]
 
 
