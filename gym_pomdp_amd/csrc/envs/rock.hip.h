@@ -313,30 +313,44 @@ struct RockEnv {
     {
         return measured < 5 && abs(count) < 2 && 0 < pv && pv < 1;
     }
-    // rock.py:177-191: side statistics of the rock a CHECK just measured (CHECK does not move the agent, so the
-    // stored position is the one the reading was taken from); keeps the rock's bit of the caller's copy of b.check_ok current
-    static __device__ __forceinline__ void belief_update(const Shared &sh, const Params &p, const State &st, int a, int ob,
-                                                         const pomdp_rock_belief &b, int64_t n, uint32_t i, uint32_t &ck)
+    // the sensor's efficiency at the agent's distance from rock r (rock.py:401-407)
+    static __device__ __forceinline__ double sensor_eff(const Shared &sh, const Params &p, const State &st, int r)
     {
         const S s = st.s;
-        const int x = (int)(s & 15u), y = (int)((s >> 4) & 15u), r = (a - 5) & 15;
+        const int x = (int)(s & 15u), y = (int)((s >> 4) & 15u);
         const uint32_t rxy = sh.rxy[r];
-        const double eff = p.eff[abs(x - (int)(rxy & 15u)) + abs(y - (int)(rxy >> 4))];
-        const int64_t k = (int64_t)r * n + i;
-        double lkv = b.lkv[k], lkw = b.lkw[k];
-        const int measured = b.measured[k] + 1;
-        int count = b.count[k];
+        return p.eff[abs(x - (int)(rxy & 15u)) + abs(y - (int)(rxy >> 4))];
+    }
+    // rock.py:177-191 on one rock's statistics, as values: the reading `ob` (1 BAD, 2 GOOD) taken with efficiency `eff` moves the
+    // count and the two likelihoods; pv is prob_valuable.  The float64 operations are the reference's, in its order.  (The
+    // caller counts the measurement.  By value, in this parameter order: the kernels compile to the text they had.)
+    struct Check { int count; double lkv, lkw, pv; };
+    static __device__ __forceinline__ Check check_update(double eff, int ob, double lkv, int count, double lkw)
+    {
         if (ob == 2) { count += 1; lkv *= eff; lkw *= (1 - eff); }
         else         { count -= 1; lkw *= eff; lkv *= (1 - eff); }
         const double denom = (.5 * lkv) + (.5 * lkw);
-        const double pv = (.5 * lkv) / denom;
+        return Check{count, lkv, lkw, (.5 * lkv) / denom};
+    }
+    // side statistics of the rock a CHECK just measured (CHECK does not move the agent, so the stored position is the one
+    // the reading was taken from); keeps the rock's bit of the caller's copy of b.check_ok current
+    static __device__ __forceinline__ void belief_update(const Shared &sh, const Params &p, const State &st, int a, int ob,
+                                                         const pomdp_rock_belief &b, int64_t n, uint32_t i, uint32_t &ck)
+    {
+        const int r = (a - 5) & 15;
+        const double eff = sensor_eff(sh, p, st, r);
+        const int64_t k = (int64_t)r * n + i;
+        const double lkv = b.lkv[k], lkw = b.lkw[k];
+        const int measured = b.measured[k] + 1;
+        const int count = b.count[k];
+        const Check u = check_update(eff, ob, lkv, count, lkw);
         b.measured[k] = measured;
-        b.count[k] = count;
-        b.lkv[k] = lkv;
-        b.lkw[k] = lkw;
-        b.prob_valuable[k] = pv;
+        b.count[k] = u.count;
+        b.lkv[k] = u.lkv;
+        b.lkw[k] = u.lkw;
+        b.prob_valuable[k] = u.pv;
         const uint32_t bit = 1u << r;                                            // the caller keeps b.check_ok[i] in `ck`
-        ck = check_ok(measured, count, pv) ? (ck | bit) : (ck & ~bit);
+        ck = check_ok(measured, u.count, u.pv) ? (ck | bit) : (ck & ~bit);
     }
 
     // rock.py:293-374 _generate_preferred with use_heuristic=True, as a bitmask over actions: every list the
@@ -410,11 +424,9 @@ struct RockEnv {
     static __device__ __forceinline__ double compute_prob(const Shared &sh, const Params &p, const State &st, int a, int ob)
     {
         if (a <= 4) return ob == 0 ? 1.0 : 0.0;
-        const S s = st.s;
-        const int x = (int)(s & 15u), y = (int)((s >> 4) & 15u), r = (a - 5) & 15;
-        const uint32_t rxy = sh.rxy[r];
-        const double eff = p.eff[abs(x - (int)(rxy & 15u)) + abs(y - (int)(rxy >> 4))];
-        const uint32_t code = (uint32_t)(s >> (8 + 2 * r)) & 3u;               // status + 1
+        const int r = (a - 5) & 15;
+        const double eff = sensor_eff(sh, p, st, r);
+        const uint32_t code = (uint32_t)(st.s >> (8 + 2 * r)) & 3u;            // status + 1
         if ((ob == 2 && code == 2u) || (ob == 1 && code == 0u)) return eff;
         return 1 - eff;
     }

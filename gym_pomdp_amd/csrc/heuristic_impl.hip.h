@@ -1,5 +1,6 @@
-// heuristic_impl.hip.h — the heuristic-policy loop: History's append on a lane's words, the side
-// statistics' update, the sinks for the loop's rows, the kernel and its launcher.  Shared by planner.hip, which instantiates
+// heuristic_impl.hip.h — the heuristic-policy loop: History's append on a lane's words, the sinks for
+// the loop's rows, the kernel and its launcher (the side statistics' update is RockEnv::belief_update, a fresh episode's
+// arrays and the sums' contributions are planner_common.hip.h's).  Shared by planner.hip, which instantiates
 // the loop that keeps nothing per step (pomdp_heuristic_steps), and heuristic_collect.hip, which instantiates it with the
 // record sinks (pomdp_heuristic_collect) — translation units of their own, so that the second family's register allocation
 // cannot disturb the first's (RockSample's sits on the 80-register edge).
@@ -9,26 +10,21 @@
 
 namespace pomdp {
 
-// the two sums over CHECK-j transitions (rock.py:303-310, 327-334) and the derived bits j and 16 + j of move_ok: the contribution of
-// one transition (action CHECK j, next observation, observation before it) is added (sign = 1) or, when a bounded history
-// drops the transition, taken out again (sign = -1)
+// check_sums applied to the history's own arrays, in place; mv: the caller's copy of h.move_ok[i]
 static __device__ __forceinline__ void history_check_sums(const pomdp_history &h, int j, int next_ob, bool prev_bad, int64_t n,
-                                                          uint32_t i, uint32_t &mv, int sign = 1)   // mv: the caller's copy of h.move_ok[i]
+                                                          uint32_t i, uint32_t &mv, int sign = 1)
 {
     const int64_t k = (int64_t)j * n + i;
-    const int ds = sign * ((next_ob == 2) - (next_ob == 1));
-    const int dm = sign * (next_ob == 2 ? 1 : (prev_bad ? -1 : 0));
-    if (ds) {                                                                  // bit 16 + j: total_sample[j] > 0 (rock.py:311)
+    const int ds = check_ds(next_ob, sign), dm = check_dm(next_ob, prev_bad, sign);
+    if (ds) {
         const int ts = h.total_sample[k] + ds;
         h.total_sample[k] = ts;
-        const uint32_t sbit = 0x10000u << j;
-        mv = ts > 0 ? (mv | sbit) : (mv & ~sbit);
+        mv = with_bit(mv, 0x10000u << j, ts > 0);
     }
     if (dm) {
         const int tm = h.total_move[k] + dm;
         h.total_move[k] = tm;
-        const uint32_t bit = 1u << j;
-        mv = tm >= 0 ? (mv | bit) : (mv & ~bit);
+        mv = with_bit(mv, 1u << j, tm >= 0);
     }
 }
 
@@ -124,29 +120,6 @@ struct HeurNarrowRows {
         row += row_bytes;
     }
 };
-
-// RockSample envs maintain side statistics; the other envs have none
-template <class Env, class = void>
-struct BeliefOps {
-    static __device__ __forceinline__ void update(const typename Env::Shared &, const typename Env::Params &,
-                                                  const typename Env::State &, int, int, const pomdp_rock_belief &, int64_t,
-                                                  uint32_t, uint32_t &) {}
-};
-template <int W, bool STOCH>
-struct BeliefOps<RockEnv<W, STOCH>, void> {
-    using Env = RockEnv<W, STOCH>;
-    static __device__ __forceinline__ void update(const typename Env::Shared &sh, const typename Env::Params &p,
-                                                  const typename Env::State &st, int a, int o, const pomdp_rock_belief &b,
-                                                  int64_t n, uint32_t i, uint32_t &ck) { Env::belief_update(sh, p, st, a, o, b, n, i, ck); }
-};
-template <class Env>
-static __device__ __forceinline__ void heuristic_belief_update(const typename Env::Shared &sh, const typename Env::Params &p,
-                                                               const typename Env::State &st, int a, int o,
-                                                               const pomdp_rock_belief &b, int64_t n, uint32_t i, uint32_t &ck)
-{
-    BeliefOps<Env>::update(sh, p, st, a, o, b, n, i, ck);
-}
-
 
 // k heuristic-policy steps in one launch: per step choice(_generate_preferred(history)) -> step -> side statistics ->
 // history.append, i.e. preferred_kernel + pick_actions_kernel + step_kernel + belief_update_kernel +
@@ -275,8 +248,8 @@ void heuristic_steps_kernel(const typename Env::Params p, uint32_t *__restrict__
                 if (fresh) {                                                   // new episode: fresh Rock objects, empty History
                     for (int j = 0; j < K; ++j) {
                         const int64_t k = (int64_t)j * n + i;
-                        b.count[k] = 0; b.measured[k] = 0; b.lkv[k] = 1.; b.lkw[k] = 1.; b.prob_valuable[k] = .5;
-                        h.total_sample[k] = 0; h.total_move[k] = 0;
+                        belief_fresh_rock(b, k);
+                        history_fresh_rock(h, k);
                     }
                     ck = mv = K ? (1u << K) - 1u : 0u;
                     hsize = 0; la = -1; lo = -1; head = 0;
@@ -285,12 +258,14 @@ void heuristic_steps_kernel(const typename Env::Params p, uint32_t *__restrict__
                     la = a; lo = o;                                            // a terminal transition is recorded too
                     if constexpr (RING) {
                         history_push<true>(h, K, a, o, pob, n, i, hsize, head, mv);
-                        if (a >= 5 && a < 5 + K && o != 0 && !d) heuristic_belief_update<Env>(sh, p, st, a, o, b, n, i, ck);
+                        if constexpr (Env::HAS_ROCKS)                          // the side statistics (the other envs have none)
+                            if (a >= 5 && a < 5 + K && o != 0 && !d) Env::belief_update(sh, p, st, a, o, b, n, i, ck);
                     } else {                                                   // no window: history_push<false>, one CHECK branch
                         hsize += (int)(hsize != hcap);
                         if (a >= 5 && a < 5 + K) {                             // K > 0: RockSample CHECK
                             history_check_sums(h, a - 5, o, pob == 1, n, i, mv);
-                            if (o != 0 && !d) heuristic_belief_update<Env>(sh, p, st, a, o, b, n, i, ck);
+                            if constexpr (Env::HAS_ROCKS)                      // the side statistics (the other envs have none)
+                                if (o != 0 && !d) Env::belief_update(sh, p, st, a, o, b, n, i, ck);
                         }
                     }
                     pob = o;
@@ -318,8 +293,6 @@ void heuristic_steps_kernel(const typename Env::Params p, uint32_t *__restrict__
     if (RING) st_stream(h.head + i, (int32_t)head);                            // without a window `head` never moves
     if (R.ret) { R.ret[i] = ret; R.disc[i] = disc; }
 }
-
-static const pomdp_rock_belief NO_BELIEF = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 
 template <class Env, class Rows = HeurNoRows, class... RowsArg>
 static int launch_heuristic_steps(const typename Env::Params &p, uint32_t *state, const pomdp_rock_belief *b,
@@ -356,7 +329,7 @@ static int history_rocks(int env, const void *params)
 {
     if (env != POMDP_ENV_ROCK) return (env >= POMDP_ENV_TAG && env <= POMDP_ENV_NETWORK) ? 0 : -1;
     const pomdp_rock_params *p = (const pomdp_rock_params *)params;
-    return (p && rock_ok(p)) ? p->num_rocks : -1;
+    return (p && rock_ok(p)) ? rock_count(*p) : -1;
 }
 
 // what pomdp_heuristic_steps and pomdp_heuristic_collect refuse alike; K = history_rocks(env, params)

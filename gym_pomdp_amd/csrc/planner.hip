@@ -50,11 +50,8 @@ __global__ __launch_bounds__(BLOCK) void belief_reset_kernel(pomdp_rock_belief b
 {
     const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n || (where && !where[i])) return;
-    for (int j = 0; j < K; ++j) {                                              // rock.py:81-86
-        const int64_t k = (int64_t)j * n + i;
-        b.count[k] = 0; b.measured[k] = 0; b.lkv[k] = 1.; b.lkw[k] = 1.; b.prob_valuable[k] = .5;
-    }
-    b.check_ok[i] = (1u << K) - 1u;                                            // a fresh rock passes the test of rock.py:371
+    for (int j = 0; j < K; ++j) belief_fresh_rock(b, (int64_t)j * n + i);
+    b.check_ok[i] = (1u << K) - 1u;
 }
 
 __global__ __launch_bounds__(BLOCK) void belief_refresh_kernel(pomdp_rock_belief b, int K, int64_t n)
@@ -82,10 +79,7 @@ __global__ __launch_bounds__(BLOCK) void belief_update_kernel(const typename Env
     if (i >= n) return;
     if (done[i]) {
         if (auto_reset) {
-            for (int j = 0; j < p.num_rocks; ++j) {
-                const int64_t k = (int64_t)j * n + i;
-                b.count[k] = 0; b.measured[k] = 0; b.lkv[k] = 1.; b.lkw[k] = 1.; b.prob_valuable[k] = .5;
-            }
+            for (int j = 0; j < p.num_rocks; ++j) belief_fresh_rock(b, (int64_t)j * n + i);
             b.check_ok[i] = (1u << p.num_rocks) - 1u;
         }
         return;
@@ -117,10 +111,7 @@ __global__ __launch_bounds__(BLOCK) void history_clear_kernel(pomdp_history h, i
 {
     const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n || (where && !where[i])) return;
-    h.size[i] = 0; h.last_action[i] = -1; h.last_ob[i] = -1;
-    for (int j = 0; j < K; ++j) { h.total_sample[(int64_t)j * n + i] = 0; h.total_move[(int64_t)j * n + i] = 0; }
-    if (K) h.move_ok[i] = (1u << K) - 1u;
-    if (h.head) h.head[i] = 0;
+    history_fresh(h, K, n, i);
 }
 
 // rock.py:541-544 History.append + the sums _generate_preferred takes over the records (rock.py:303-310, 327-334)
@@ -132,10 +123,7 @@ __global__ __launch_bounds__(BLOCK) void history_append_kernel(pomdp_history h, 
     const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
     if (done[i] && auto_reset) {                                               // next episode: a new, empty History
-        h.size[i] = 0; h.last_action[i] = -1; h.last_ob[i] = -1;
-        for (int j = 0; j < K; ++j) { h.total_sample[(int64_t)j * n + i] = 0; h.total_move[(int64_t)j * n + i] = 0; }
-        if (K) h.move_ok[i] = (1u << K) - 1u;
-        if (h.head) h.head[i] = 0;
+        history_fresh(h, K, n, i);
         return;
     }
     const int a = action[i], o = next_observation[i];
@@ -249,10 +237,8 @@ __global__ __launch_bounds__(BLOCK) void rollout_kernel(const typename Env::Para
             const int count = all_actions ? n_act : L.count;
             active = active && !d && count > 0;
             if (!__any(active)) { live_wave = false; return; }           // wave-uniform exit
-            const uint64_t t = t0 + (uint64_t)step;
-            RngKey key = key0;
-            key.t_lo = (uint32_t)t; key.t_hi = (uint32_t)(t >> 32);
-            const uint32_t w = J == 0 ? pw.x : J == 1 ? pw.y : J == 2 ? pw.z : pw.w;
+            const RngKey key = key_at(key0, t0 + (uint64_t)step);
+            const uint32_t w = comp<J>(pw);
             const int idx = (int)__umulhi(w, (uint32_t)(count > 0 ? count : 1));
             const int a = all_actions ? idx : LegalOf<Env>::pick(sh, p, st, L, idx);
             typename Env::State nx = st;
@@ -492,16 +478,10 @@ int pomdp_plan(int env, const void *params, const uint32_t *root_state, int64_t 
                double discount, int flags, uint64_t seed, uint32_t lane0, uint64_t t0, double *sim_ret,
                int32_t *sim_first_action, const pomdp_plan_out *out, void *stream)
 {
-    if (!params || !out) return POMDP_E_BADARG;
-    // everything is checked before anything is enqueued
-    int rc = dispatch_env(env, params, [](auto, const auto &) { return 0; });   // POMDP_E_BADPARAMS / unknown env
-    if (rc) return rc;
-    const int n_act = (int)env_action_count(env, params);
-    if (n_roots > 0x7FFFFFFF || !plan_out_ok(out, n_act)) return POMDP_E_BADARG;
-    rc = pomdp_rollout(env, params, root_state, n_roots, sims_per_root, depth, discount, flags, seed, lane0, t0, sim_ret, nullptr,
-                       sim_first_action, nullptr, nullptr, stream);
-    if (rc) return rc;
-    return pomdp_plan_reduce(sim_ret, sim_first_action, n_roots, sims_per_root, n_act, out, stream);
+    return plan_with(env, params, n_roots, sims_per_root, sim_ret, sim_first_action, out, stream, [&]() {
+        return pomdp_rollout(env, params, root_state, n_roots, sims_per_root, depth, discount, flags, seed, lane0, t0, sim_ret,
+                             nullptr, sim_first_action, nullptr, nullptr, stream);
+    });
 }
 
 int pomdp_rock_belief_reset(const pomdp_rock_params *p, const pomdp_rock_belief *b, const uint8_t *where, int64_t n,

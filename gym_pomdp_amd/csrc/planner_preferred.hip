@@ -9,8 +9,6 @@ namespace pomdp {
 
 // envs whose _generate_preferred is a policy of its own (RockSample's heuristic, Tag); for the others it is the legal list
 template <class Env> struct has_policy : std::integral_constant<bool, Env::HAS_ROCKS || std::is_same<Env, TagEnv>::value> {};
-template <class Env, bool ROCKS = Env::HAS_ROCKS> struct rocks_of { static __device__ __forceinline__ int get(const typename Env::Params &) { return 0; } };
-template <class Env> struct rocks_of<Env, true> { static __device__ __forceinline__ int get(const typename Env::Params &p) { return p.num_rocks; } };
 
 // rollout_kernel under the env's preferred-action policy (include/pomdp_hip.h: pomdp_rollout_preferred): the same lanes,
 // words, step and return, with the list of step k being _generate_preferred(history) of the SIMULATION's own statistics and
@@ -49,7 +47,7 @@ __global__ __launch_bounds__(BLOCK) void rollout_preferred_kernel(const typename
         Env::build_rec_tab(tab, sh, p, (int)threadIdx.x);
         __syncthreads();
     }
-    const int K = rocks_of<Env>::get(p);
+    const int K = rock_count(p);
     const int64_t n = n_roots * sims_per_root;
     const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     const bool in_range = i < n;
@@ -84,9 +82,7 @@ __global__ __launch_bounds__(BLOCK) void rollout_preferred_kernel(const typename
             const int count = m ? __popc(m) : L.count;
             active = active && !d && count > 0;
             if (!__any(active)) { live_wave = false; return; }           // wave-uniform exit
-            const uint64_t t = t0 + (uint64_t)step;
-            RngKey key = key0;
-            key.t_lo = (uint32_t)t; key.t_hi = (uint32_t)(t >> 32);
+            const RngKey key = key_at(key0, t0 + (uint64_t)step);
             const uint32_t w = comp<J>(pw);
             const int idx = (int)__umulhi(w, (uint32_t)(count > 0 ? count : 1));
             const int a = m ? nth_set_bit(m, idx) : LegalOf<Env>::pick(sh, p, st, L, idx);
@@ -133,22 +129,14 @@ __global__ __launch_bounds__(BLOCK) void rollout_preferred_kernel(const typename
                             cnt = b.count[kr]; meas = b.measured[kr]; ts = h.total_sample[kr]; tm = h.total_move[kr];
                             lkv = b.lkv[kr]; lkw = b.lkw[kr];
                         }
-                        // history_check_sums on the private entry (rock.py:303-310, 327-334)
-                        const int ds = (o2 == 2) - (o2 == 1);
-                        const int dm = o2 == 2 ? 1 : (pob == 1 ? -1 : 0);
-                        if (ds) { ts += ds; mv = ts > 0 ? (mv | (bit << 16)) : (mv & ~(bit << 16)); }
-                        if (dm) { tm += dm; mv = tm >= 0 ? (mv | bit) : (mv & ~bit); }
-                        if (o2 != 0 && !d2) {                            // Env::belief_update (rock.py:177-191); CHECK does not move
-                            const auto s = st.s;
-                            const int x = (int)(s & 15u), y = (int)((s >> 4) & 15u);
-                            const uint32_t rxy = sh.rxy[j & 15];
-                            const double eff = p.eff[abs(x - (int)(rxy & 15u)) + abs(y - (int)(rxy >> 4))];
-                            meas += 1;
-                            if (o2 == 2) { cnt += 1; lkv *= eff; lkw *= (1 - eff); }
-                            else         { cnt -= 1; lkw *= eff; lkv *= (1 - eff); }
-                            const double denom = (.5 * lkv) + (.5 * lkw);
-                            const double pv = (.5 * lkv) / denom;
-                            ck = Env::check_ok(meas, cnt, pv) ? (ck | bit) : (ck & ~bit);
+                        // the history's two sums and Env::belief_update, on the private entry
+                        const int ds = check_ds(o2), dm = check_dm(o2, pob == 1);
+                        if (ds) { ts += ds; mv = with_bit(mv, bit << 16, ts > 0); }
+                        if (dm) { tm += dm; mv = with_bit(mv, bit, tm >= 0); }
+                        if (o2 != 0 && !d2) {                            // CHECK does not move: st is where the reading was taken
+                            const auto u = Env::check_update(Env::sensor_eff(sh, p, st, j & 15), o2, lkv, cnt, lkw);
+                            meas += 1; cnt = u.count; lkv = u.lkv; lkw = u.lkw;
+                            ck = with_bit(ck, bit, Env::check_ok(meas, cnt, u.pv));
                         }
                         ws_stat[ks] = make_int4(cnt, meas, ts, tm);
                         ws_lkv[ks] = lkv; ws_lkw[ks] = lkw;
@@ -172,8 +160,6 @@ __global__ __launch_bounds__(BLOCK) void rollout_preferred_kernel(const typename
     }
 }
 
-static inline int rock_count(const pomdp_rock_params &p) { return p.num_rocks; }
-template <class P> static inline int rock_count(const P &) { return 0; }
 // the arguments are checked by the entry point
 template <class Env>
 static int launch_rollout_preferred(const typename Env::Params &p, const uint32_t *state, int64_t n_roots, int n_particles,
@@ -184,12 +170,11 @@ static int launch_rollout_preferred(const typename Env::Params &p, const uint32_
 {
     const int64_t n = n_roots * sims;
     if (n == 0) return 0;
-    static const pomdp_rock_belief NONE = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     const int64_t cells = Env::HAS_ROCKS ? n * rock_count(p) : 0;          // workspace: int4 [K][n], then lkv, lkw double [K][n]
     int4 *const ws_stat = (int4 *)workspace;
     double *const ws_lkv = (double *)(ws_stat + cells);
     hipLaunchKernelGGL(rollout_preferred_kernel<Env>, dim3(blocks_for(n)), dim3(BLOCK), 0, (hipStream_t)stream, p, state, n_roots,
-                       sims, sims / n_particles, depth, discount, (Env::HAS_ROCKS && b) ? *b : NONE, *h, prev_ob, ws_stat, ws_lkv,
+                       sims, sims / n_particles, depth, discount, (Env::HAS_ROCKS && b) ? *b : NO_BELIEF, *h, prev_ob, ws_stat, ws_lkv,
                        ws_lkv + cells, make_key(seed, t0), lane0, ret, n_steps, first_action, last_ob, terminated);
     return (int)hipGetLastError();
 }
@@ -233,16 +218,10 @@ int pomdp_plan_preferred(int env, const void *params, const uint32_t *state, int
                          const int32_t *prev_ob, void *workspace, uint64_t seed, uint32_t lane0, uint64_t t0, double *sim_ret,
                          int32_t *sim_first_action, const pomdp_plan_out *out, void *stream)
 {
-    if (!params || !out) return POMDP_E_BADARG;
-    // everything is checked before anything is enqueued
-    int rc = dispatch_env(env, params, [](auto, const auto &) { return 0; });   // POMDP_E_BADPARAMS / unknown env
-    if (rc) return rc;
-    const int n_act = (int)env_action_count(env, params);
-    if (n_roots > 0x7FFFFFFF || !plan_out_ok(out, n_act)) return POMDP_E_BADARG;
-    rc = pomdp_rollout_preferred(env, params, state, n_roots, n_particles, sims_per_root, depth, discount, b, h, prev_ob, workspace,
-                                 seed, lane0, t0, sim_ret, nullptr, sim_first_action, nullptr, nullptr, stream);
-    if (rc) return rc;
-    return pomdp_plan_reduce(sim_ret, sim_first_action, n_roots, sims_per_root, n_act, out, stream);
+    return plan_with(env, params, n_roots, sims_per_root, sim_ret, sim_first_action, out, stream, [&]() {
+        return pomdp_rollout_preferred(env, params, state, n_roots, n_particles, sims_per_root, depth, discount, b, h, prev_ob,
+                                       workspace, seed, lane0, t0, sim_ret, nullptr, sim_first_action, nullptr, nullptr, stream);
+    });
 }
 
 } // extern "C"
