@@ -33,51 +33,7 @@ __global__ __launch_bounds__(BLOCK) void reset_where_kernel(const typename Env::
     if (ob) ob[i] = o;
 }
 
-// ---- the returns sink of a frozen-lane loop ---------------------------------------------------------------------------------
-// The statistics of pomdp_return_stats, LPT lanes per thread, in ReturnsRegs (traj_out.hip.h).  A live step adds its reward and
-// banks the return when it ends the episode — as pomdp_collect_returns does — and counts one step; a frozen lane adds
-// nothing.  What is this sink's own: `steps` is kept in a register and stored once, like the rest.
-template <class Env, int LPT>
-struct EpisodeReturns {
-    ReturnsRegs<Env, LPT> regs;
-    uint32_t steps[LPT];
-    __device__ __forceinline__ EpisodeReturns(double *acc, uint32_t *cnt, uint64_t discount_bits, int64_t pitch)
-        : regs(acc, cnt, discount_bits, pitch) {}
-    __device__ __forceinline__ void begin(int j, uint32_t i)
-    {
-        regs.load_lane(j, i);
-        steps[j] = ld_stream(regs.cnt_w + regs.pitch + i);
-    }
-    // the same for a quad of consecutive lanes l0 .. l0 + 3 (LPT = 4, rows on 16-byte boundaries): 16-byte accesses — four
-    // scalar 8-byte streamed accesses per row and quad cost the quad loop's first 16-step launch a third of its time
-    __device__ __forceinline__ void begin4(uint32_t l0)
-    {
-        static_assert(LPT == 4, "a quad per thread");
-        regs.load_row(l0);
-        const u32x4 n = ld_stream4(regs.cnt_w + regs.pitch + l0);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) steps[j] = n[j];
-    }
-    __device__ __forceinline__ void finish4(uint32_t l0)
-    {
-        static_assert(LPT == 4, "a quad per thread");
-        regs.store_row(l0);
-        st_stream4(regs.cnt_w + regs.pitch + l0, steps[0], steps[1], steps[2], steps[3]);
-    }
-    // `record`: the step's packed record (action | ob << 8 | reward code << 16 | done << 24)
-    __device__ __forceinline__ void put(int j, uint32_t record, bool live)
-    {
-        if (live) {
-            regs.step_record(j, record);
-            ++steps[j];
-        }
-    }
-    __device__ __forceinline__ void finish(int j, uint32_t i)
-    {
-        regs.store_lane(j, i);
-        st_stream(regs.cnt_w + regs.pitch + i, steps[j]);
-    }
-};
+// the returns sink of these loops: EpisodeReturns (traj_out.hip.h), shared with controller.hip
 
 // ---- the general frozen-lane loop: one lane per thread, any n, every env ----------------------------------------------------
 // k_steps consecutive pomdp_<env>_step(flags = 0) calls at t0 + s with the synthetic policy's actions of t0 + s (TAPE: row s of

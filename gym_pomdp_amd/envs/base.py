@@ -1111,6 +1111,64 @@ class BatchedEnv(compat.EnvBase):
         self.done = self._done_bool
         return result
 
+    def run_controller(self, ctrl, steps, layout="returns", out=None, stats=None):
+        """finish_episodes under a policy that reacts to what each lane observes: `steps` consecutive step() calls of an
+        auto_reset=False env in one fused loop (pomdp_controller_episodes), lane i taking ctrl.action[ctrl.node[i]] and then
+        moving to ctrl.next[ctrl.node[i]][ob] (`ctrl`: a gym_pomdp_amd.Controller of this env; ctrl.node is updated in place,
+        so a later call goes on where this one stopped).  Same draws as step() at the same call counters, same frozen rows,
+        layouts, `out` / `stats` and return values as finish_episodes; env.done is updated in place.  An entry a
+        validate=False controller should not hold — an action out of range, a successor that is no node — is handled as
+        include/pomdp_hip.h says and counted in invalid_action_count().  Then ctrl.reset_nodes(where=env.done) followed by
+        reset(where=env.done) restarts the finished lanes (in that order: the reset clears env.done).  auto_reset=False envs
+        only.  Asynchronous."""
+        if not self._has_reset:
+            raise AttributeError("%s: run_controller before reset()" % type(self).__name__)
+        if self.auto_reset:
+            raise ValueError("run_controller needs auto_reset=False (an auto-reset env never finishes)")
+        self._check_driver_use("run_controller")
+        n = self.batch_size
+        if n == 1:
+            raise ValueError("run_controller: a batch of one keeps its done flag on the host — use step()")
+        if getattr(ctrl, "env", None) is not self:
+            raise ValueError("run_controller: `ctrl` was built for another env")
+        if stats is not None:
+            layout = "returns"
+        elif out is not None:
+            layout = out.get("layout", "columns")
+        if layout not in ("returns", "packed", "narrow"):
+            raise ValueError("run_controller: layout must be 'returns', 'packed' or 'narrow', got %r" % (layout,))
+        steps = int(steps)
+        args = _native.EpisodeArgs(env=_native.ENV_KIND[self.env_name], layout=0, params=C.addressof(self._params),
+                                   state=self._ptrs[0], done=self._ptrs[3], tape=None, traj=None, pitch=0, stats=None,
+                                   err=self._ptrs[4], n=n, seed=self._seed, lane0=self.lane_offset, reserved=0)
+        cargs = _native.Controller(action=ctrl.action.data_ptr(), next=ctrl.next.data_ptr(), n_nodes=ctrl.n_nodes, n_obs=ctrl.n_obs,
+                                   node=ctrl.node.data_ptr())
+        with torch.cuda.device(self.device):
+            if layout == "returns":
+                if stats is None:
+                    from ..history import EpisodeStats
+                    stats = EpisodeStats(self)
+                elif stats._n != n or stats.acc.device != self.device:
+                    raise ValueError("run_controller: `stats` belongs to another batch")
+                args.layout, args.stats = _native.POMDP_LAYOUT_RETURNS, C.addressof(stats._ptrs)
+                result = stats
+            else:
+                if out is None:
+                    out = self.trajectory_buffers(steps, layout)
+                traj, pitch = out["traj"], int(out["pitch"])
+                row = {"packed": (pitch,), "narrow": (4, pitch)}[layout]
+                if not (traj.shape[0] >= steps and tuple(traj.shape[1:]) == row and traj.is_contiguous() and pitch >= n
+                        and traj.dtype == (torch.int32 if layout == "packed" else torch.uint8)):
+                    raise ValueError("run_controller: `out` does not have the shape of trajectory_buffers(%d, %r)" % (steps, layout))
+                args.layout, args.traj, args.pitch = _native.LAYOUTS[layout], traj.data_ptr(), pitch
+                result = out
+            t0 = self._t
+            self._t = t0 + steps
+            rc = self._lib.pomdp_controller_episodes(C.byref(args), C.byref(cargs), t0, steps, self._stream())
+            _native.check(rc, "pomdp_controller_episodes")
+        self.done = self._done_bool
+        return result
+
     def _check_driver_use(self, what):
         """The C-side episode loops advance the packed state only: they know nothing of RockSample's side statistics
         (use_heuristic / track_belief envs), and the synthetic policy shares one Philox block among global lanes

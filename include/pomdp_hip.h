@@ -447,6 +447,43 @@ typedef struct pomdp_episode_args {
 } pomdp_episode_args;
 int pomdp_finish_episodes(const pomdp_episode_args *a, uint64_t t0, int64_t k_steps, void *stream);
 
+/* pomdp_controller_episodes: pomdp_finish_episodes under a policy that REACTS to what the lane observes — a finite-state
+ * controller: K nodes, an action per node, a successor node per (node, observation).  A memoryless ob -> action table, an
+ * open-loop or periodic plan and any finite-memory policy are such controllers; several of them side by side (disjoint node
+ * ranges) are one, so a population is evaluated in one call by starting each lane in its own controller's range.  The
+ * tables are staged into the workgroup's LDS once per launch (action as a byte, next as a halfword); a lane's node is one
+ * register next to its state.  Frozen mode only (flags = 0 semantics, one episode per lane); `a` is read as by
+ * pomdp_finish_episodes — layouts POMDP_LAYOUT_PACKED / _NARROW / _RETURNS, `done` in/out — and a->tape must be NULL.  Step s
+ * runs at call counter t0 + s on the env's draws of (seed, lane, t0 + s), those of every other path.  Per lane and step:
+ *   - a live lane takes action[node]; its record is the real one; then node = next[node][ob] — also on the step that ends the
+ *     episode, after which the lane is frozen;
+ *   - a frozen lane does not step; state and node are untouched; its record is action[node] | 1 << 24, the action byte being
+ *     what a per-step caller would pass; nothing is counted;
+ *   - a live lane whose action[node] is outside the env's action range is untouched for that step: record = the action byte,
+ *     (ob, reward, done) = (0, 0, 0), the node unchanged, counted in *a->err, and the returns sink books a step with reward 0
+ *     (the tape contract);
+ *   - a live lane whose next[node][ob] is outside [0, n_nodes): the step stands, the node stays where it was, counted in
+ *     *a->err (an observation the table has no column for — Tag with obs_cells < 28 — finds no successor either);
+ *   - a lane whose incoming node[i] is outside [0, n_nodes) is treated like an out-of-range action on every step: untouched
+ *     and counted while live, node[i] left as it was.
+ * The action byte of a record is action[node] where that lies in [0, 255] and 255 otherwise (a value that does not fit a byte,
+ * or no node at all) — the rule of a tape byte; 255 is out of range for every env.  No table entry and no node value makes
+ * the kernel read outside its tables.
+ * Any n; lane0 a multiple of 4; up to pomdp_fuse_max() steps per launch, `node` read when a launch starts and written when
+ * it ends, so results never depend on the chunking.  Refused before anything is enqueued (POMDP_E_BADARG / _BADPARAMS):
+ * everything pomdp_finish_episodes refuses; NULL c, action, next or node; n_nodes or n_nodes * n_obs past the limits below;
+ * n_obs other than the env's observation count (RockSample 3, Tag obs_cells + 1, BattleShip 2, Tiger 3, Network 3); a->tape
+ * not NULL; Tag with obs_cells > 255 for the record sinks.  k_steps == 0 or n == 0: 0, nothing launched.  The caller's call
+ * counter advances by k_steps. */
+typedef struct pomdp_controller {
+    const int32_t *action;   /* device [n_nodes]: the action of node q */
+    const int32_t *next;     /* device [n_nodes][n_obs]: successor of node q on observation o */
+    int32_t  n_nodes, n_obs; /* 1 <= n_nodes <= 4096, n_nodes * n_obs <= 16384; n_obs = the env's observation count */
+    int32_t *node;           /* device [n], in/out: lane i's current node */
+} pomdp_controller;
+int pomdp_controller_episodes(const pomdp_episode_args *a, const pomdp_controller *c,
+                              uint64_t t0, int64_t k_steps, void *stream);
+
 /* Steps per fused launch of the C-side drivers above (pomdp_rollout_synthetic with POMDP_FUSE_STEPS, pomdp_collect_*,
  * pomdp_heuristic_steps): a launch's fixed cost (kernel start, table build, drain) is paid once per this many steps.
  * pomdp_fuse_max(v) sets it for the calling process (1 <= v <= 256; v <= 0 only reads) and returns the previous value;
