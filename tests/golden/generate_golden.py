@@ -15,7 +15,8 @@ Fixtures:
   F5  edge_cases.json    error behaviour of the reference at the boundary
       live_<id>.npz      modes A and B on seeds drawn once, in configurations
                          of no other fixture (tests/test_reference_live.py;
-                         --live-only writes these alone)
+                         --live-only writes these alone, --live-from=<i>
+                         with it only those from index i on)
       edge_<env>.npz     mode B at the edges of the Philox key and counter: a
                          seed with both key words set, lanes up to 0xFFFFFFFF,
                          a call counter that crosses 2^32 (--key-edges-only)
@@ -256,7 +257,13 @@ def gen_heuristic(case, env, kwargs, L, T, max_size=None):
 LIVE_CASES = [("rock", {}), ("rock", dict(board_size=11, num_rocks=11)), ("stochrock", {}), ("tag", {}),
               ("tag", dict(num_opponents=3)), ("tag", dict(move_prob=.3)), ("tag", dict(num_opponents=2, move_prob=.55)), ("battleship", {}),
               ("battleship", dict(board_size=(7, 9), max_len=4)), ("tiger", {}), ("network", {}),
-              ("network", dict(n_machines=13, problem_type=3)), ("network", dict(n_machines=7, problem_type=2))]
+              ("network", dict(n_machines=13, problem_type=3)), ("network", dict(n_machines=7, problem_type=2)),
+              # appended (ids and seeds go by index): the constructor parameters tests/test_gpu_env_params.py launches with
+              ("stochrock", dict(p_move=.5)), ("stochrock", dict(p_move=.95)),
+              ("tag", dict(move_prob=.5)), ("tag", dict(num_opponents=4, move_prob=.4)), ("tag", dict(obs_cells=64)),
+              ("network", dict(n_machines=1, problem_type=2)), ("network", dict(n_machines=4, problem_type=3)),
+              ("network", dict(n_machines=9, problem_type=1)), ("network", dict(n_machines=17, problem_type=1)),
+              ("network", dict(n_machines=25, problem_type=3)), ("network", dict(n_machines=32, problem_type=2))]
 LIVE_MODE_A = (4, 400)            # seeds, steps per seed
 LIVE_MODE_B = (2, 12, 40)         # draws of (seed, lane0, t0), lanes, steps per draw
 
@@ -412,7 +419,10 @@ def main():
     import warnings
     warnings.simplefilter("ignore", RuntimeWarning)  # reference's belief side-stats divide 0/0 (rock.py:191)
     if "--live-only" in sys.argv:
+        first = [int(a.split("=", 1)[1]) for a in sys.argv if a.startswith("--live-from=")]     # --live-from=<index>: appended cases alone
         for i, (env, kwargs) in enumerate(LIVE_CASES):
+            if first and i < first[0]:
+                continue
             print("live %-22s modeA dones=%4d  modeB dones=%4d" % gen_live(i, env, kwargs), flush=True)
         return
     if "--key-edges-only" in sys.argv:

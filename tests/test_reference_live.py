@@ -13,7 +13,13 @@ from conftest import GOLDEN
 CASES = [("rock", {}), ("rock", dict(board_size=11, num_rocks=11)), ("stochrock", {}), ("tag", {}),
          ("tag", dict(num_opponents=3)), ("tag", dict(move_prob=.3)), ("tag", dict(num_opponents=2, move_prob=.55)), ("battleship", {}), ("battleship", dict(board_size=(7, 9), max_len=4)),
          ("tiger", {}), ("network", {}), ("network", dict(n_machines=13, problem_type=3)),
-         ("network", dict(n_machines=7, problem_type=2))]
+         ("network", dict(n_machines=7, problem_type=2)),
+         # the constructor parameters tests/test_gpu_env_params.py launches with
+         ("stochrock", dict(p_move=.5)), ("stochrock", dict(p_move=.95)),
+         ("tag", dict(move_prob=.5)), ("tag", dict(num_opponents=4, move_prob=.4)), ("tag", dict(obs_cells=64)),
+         ("network", dict(n_machines=1, problem_type=2)), ("network", dict(n_machines=4, problem_type=3)),
+         ("network", dict(n_machines=9, problem_type=1)), ("network", dict(n_machines=17, problem_type=1)),
+         ("network", dict(n_machines=25, problem_type=3)), ("network", dict(n_machines=32, problem_type=2))]
 IDS = ["%s-%d" % (c[0], i) for i, c in enumerate(CASES)]
 
 
