@@ -14,6 +14,12 @@ namespace pomdp {
 // the loop.  The returns sinks of StochasticRock and BattleShip sit at 120-128 registers, four waves per SIMD (their sink keeps
 // 40 per thread): they keep the product in the step (hoist_fits), and so does the gate and sensor block of the former.
 template <class L, bool TIGHT> constexpr bool hoist_fits = !(TIGHT && L::ID == LAYOUT_RETURNS);
+// UNDER_READS (steps_quad_body): RockSample's one-state-word loops issue the synthetic policy's block under the lane step's table
+// reads, and its four actions then live across the records — four more registers.  No loop may pay for that with a wave per SIMD:
+// StochasticRock's returns sink (126 registers, 130 with it: three waves instead of four) and its column sink (94, 98 with it:
+// four instead of five) keep the block where the compiler puts it.  tests/test_quad_loop_schedule_host.py holds every loop to
+// the occupancy it had.
+template <class L, bool STOCH> constexpr bool under_reads_fits = !(STOCH && (L::ID == LAYOUT_RETURNS || L::ID == POMDP_LAYOUT_COLUMNS));
 template <class L, class Pol, int LPT = 4, bool SROW = false, bool HOIST = true>   // SROW: packed records leave through a scalar row base (traj_out.hip.h)
 struct FusedCtx {
     uint32_t l0, glane0;                                     // the thread's first lane within the shard / its global id
@@ -362,7 +368,9 @@ __global__ __launch_bounds__(BLOCK) void steps_kernel(uint32_t *__restrict__ sta
 // STEP block — which a done step's auto-reset reads as well (rock.hip.h) — and the policy's ACTION block among the four
 // lanes of a quad, so with this mapping both are the thread's own: two Philox blocks per thread-step straight into
 // registers, lane j taking element j — no exchange through LDS, no ballots, no task lists, and no dependence on the lane
-// step: the compiler interleaves the chains with the table lookups.  A thread's outputs are four consecutive elements of each column: one 16-byte store per
+// step.  (The compiler does NOT interleave the chains with the table lookups by itself: it sinks the policy's block to where its
+// words are used, below the records.  The one-state-word path places it under the table reads by hand — UNDER_READS in the
+// step body; tests/test_quad_loop_schedule_host.py reads the compiled loop.)  A thread's outputs are four consecutive elements of each column: one 16-byte store per
 // int32 column and one 4-byte store of the packed done bytes per step instead of twenty scalar stores; state and first
 // actions come in the same way.  The lane step is the table-driven one.  Full workgroups of 1024 lanes and auto-reset
 // only (the launcher's SIMPLE conditions).  Same results as steps_kernel: the mapping of lanes to threads is invisible
@@ -473,9 +481,13 @@ __device__ __forceinline__ void steps_quad_body(uint32_t *__restrict__ state, in
         } else {
             pair_shared(s, e0 != 0u, [&](int sb) { return Env::quad_block(cx.key(key0, sb), glane0, SENSOR_BLOCK); }, H, sp0, sp1);
         }
+        // One state word, synthetic policy: the policy's block does not depend on the step's state, so it is issued UNDER the
+        // table reads — after the last of them, in front of the one wait (UNDER_READS below) — where four more live registers
+        // cost no wave (under_reads_fits); a tape's row is asked for here
         uint32_t a_next[LPT];
+        constexpr bool UNDER_READS = W == 1 && !Pol::TAPE && under_reads_fits<L, Env::STOCHASTIC>;
         if constexpr (AHEAD2) cx.pol.template begin_par<PAR>(s, a_next);
-        else cx.pol.begin(s, a_next);
+        else if constexpr (!UNDER_READS) cx.pol.begin(s, a_next);
         // (a lane's step draws EITHER its sensor reading OR its next episode: the fresh episodes start from the same words, R = H)
         bool acts[LPT];
 #pragma unroll
@@ -511,6 +523,10 @@ __device__ __forceinline__ void steps_quad_body(uint32_t *__restrict__ state, in
             Form::template fresh<LPT>(H, key, glane0, K, start_rot, tie_bound, fresh);
 #pragma unroll
             for (int j = 0; j < LPT; ++j) ef[j] = Form::lookup(tab, st[j].s, valid[j] ? a_taken[j] : 0u);
+            // the reads are in flight: the actions of step s + 1, finished (pin_words) before the wait — left to itself the
+            // compiler sinks the block below the records, and the wave sits through the LDS round trip with nothing to issue
+            // (the scheduling barrier keeps the last reads from drifting down into the block)
+            if constexpr (UNDER_READS) { __builtin_amdgcn_sched_barrier(0); cx.pol.begin(s, a_next); pin_words(a_next); }
             Form::template settle<LPT>(ef);                                 // all of them have landed: one wait
             // H - e with its borrow: the borrow IS `correct` = H < e, the difference feeds the filter (one v_sub_co_u32 per lane)
             uint32_t near[LPT];

@@ -343,6 +343,14 @@ static __device__ __forceinline__ uint4 quad_transpose4(const uint4 &v, uint32_t
 // stores, every step.  (It settles them in the pre-header by itself only when the loop has a single entry; the priority
 // ladder below gives it two.)  s_waitcnt vmcnt(0) expcnt(7) lgkmcnt(15) on gfx9.
 static __device__ __forceinline__ void wait_loads() { __builtin_amdgcn_s_waitcnt(0x0F70); }
+// The words stand finished in vector registers HERE: a pin in front of another pinned point (a table wait) keeps the arithmetic
+// that makes them from sinking past it.  No instruction of its own.
+template <int N> static __device__ __forceinline__ void pin_words(uint32_t (&w)[N])
+{
+    static_assert(N == 4 || N == 2, "a quad's words or half a quad's");
+    if constexpr (N == 4) asm volatile("" : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]));
+    else asm volatile("" : "+v"(w[0]), "+v"(w[1]));
+}
 
 // Issue priority of a wave inside a fused step loop (round 3, profiles/r03_prio_timeline.txt).  A SIMD's arbiter serves its
 // OLDEST wave first: of the four workgroups a CU holds, the first ran its 64 steps almost as if alone (1.3 us per step, done

@@ -55,6 +55,40 @@ def loop_waits(text):
     return res
 
 
+def kernel_bodies(text):
+    """-> {demangled kernel name: its lines}"""
+    lines = text.split("\n")
+    heads = [(i, m.group(1)) for i, l in enumerate(lines) for m in [re.match(r"^(_Z\w+):", l)] if m]
+    dem = subprocess.run(["c++filt"], input="\n".join(n for _, n in heads), capture_output=True, text=True).stdout.splitlines()
+    ends = [i for i, _ in heads[1:]] + [len(lines)]
+    return {d: lines[i:e] for (i, _), d, e in zip(heads, dem, ends)}
+
+
+def under_reads(body, read):
+    """What a loop issues between a group of LDS reads `read` (e.g. "ds_read_b128") and the `s_waitcnt lgkmcnt` that follows it:
+    -> [(reads in the group, Philox instructions — v_mad_u64_u32 / v_bitop3_b32 — after the group's LAST read, branches met)],
+    one entry per group that sits in a loop block.  A synthetic policy's block issued under the table reads of the quad loops
+    (fused_impl.hip.h: UNDER_READS) shows as (4, 30, 0): 15 + 15, nothing of it in front of the last read."""
+    out, in_loop, j = [], False, 0
+    while j < len(body):
+        l = body[j]
+        if re.match(r"^\.LBB\d+_\d+:", l) or l.startswith("; %bb."):
+            in_loop = "Loop" in l
+        if in_loop and l.strip().startswith(read):
+            reads, philox, branches = 1, 0, 0
+            for j in range(j + 1, len(body)):
+                s = body[j].strip()
+                if s.startswith("s_waitcnt") and "lgkmcnt" in s:
+                    break
+                if s.startswith(read):
+                    reads, philox = reads + 1, 0
+                philox += s.startswith(("v_mad_u64_u32", "v_bitop3_b32"))
+                branches += s.startswith(("s_cbranch", "s_branch"))
+            out.append((reads, philox, branches))
+        j += 1
+    return out
+
+
 def main(units):
     bad = 0
     with ThreadPoolExecutor(max_workers=4) as ex:

@@ -8,7 +8,7 @@
 #   (packed, columns, blocked, narrow, returns) x (256, 20) steps per launch + HBM byte passes; envs = the other envs' fused
 #   launches (packed and columns); shards = RockSample(7,8) at 2^17 / 2^18 / 2^19 lanes; packed = the headline kernel alone
 #   (RockSample(7,8), packed records, both launch shapes) with its HBM byte passes: what a change to the lane step re-records;
-#   heuristic = the heuristic loops of `planners` without the rollouts.
+#   heuristic = the heuristic loops of `planners` without the rollouts; loop = the headline kernel's 256-step launch alone.
 #   Workloads that are not re-recorded are carried over from the newest profiles/*_pmc_valu.json, each with the source hash
 #   it was recorded under (bench.py: counters_stale).
 TAG=${1:-pmcv}
@@ -88,6 +88,8 @@ for set in $SETS; do
     run step20_rock_packed --env rock --layout packed $S20
     traffic step20_rock_packed --env rock --layout packed $S20
     traffic step256_rock_packed --env rock --layout packed $S256 ;;
+  loop)     # the headline kernel's 256-step launch alone, two counter passes: the A/B of a change to how its loop is scheduled
+    run step256_rock_packed --env rock --layout packed $S256 ;;
   sinks)    # the headline workload's sinks at 256 steps per launch only (a quick A/B of what a sink costs)
     for l in packed narrow returns; do run step256_rock$(sfx $l) --env rock --layout $l $S256; done ;;
   envs)
