@@ -17,8 +17,8 @@ LIB_PATH = os.environ.get("GYM_POMDP_AMD_LIB") or INTREE_LIB_PATH
 # one object per translation unit (built in parallel), linked into one shared library
 UNITS = ["api.hip", "step_rock.hip", "step_other.hip", "fused_rock.hip", "fused_stochrock.hip", "fused_tag.hip",
          "fused_battleship.hip", "fused_misc.hip", "planner.hip", "episodes.hip",
-         "particles.hip", "planner_preferred.hip", "heuristic_collect.hip", "controller.hip"]
-HEADERS = ["kernels_common.hip.h", "planner_common.hip.h", "heuristic_impl.hip.h", "traj_out.hip.h", "step_impl.hip.h", "fused_impl.hip.h", "envs.hip.h", "envs_common.hip.h", "philox.hip.h",
+         "particles.hip", "planner_preferred.hip", "heuristic_collect.hip", "controller.hip", "tree_search.hip"]
+HEADERS = ["kernels_common.hip.h", "planner_common.hip.h", "heuristic_impl.hip.h", "traj_out.hip.h", "step_impl.hip.h", "fused_impl.hip.h", "envs.hip.h", "envs_common.hip.h", "philox.hip.h", "tree_pool.hip.h",
            "envs/rock.hip.h", "envs/tag.hip.h", "envs/battleship.hip.h", "envs/tiger.hip.h", "envs/network.hip.h"]
 SOURCES = [os.path.join(_PKG, "csrc", f) for f in UNITS + HEADERS]
 HEADER = os.path.join(_REPO, "include", "pomdp_hip.h")
@@ -45,6 +45,7 @@ SYMBOLS = [
     "pomdp_reset_where", "pomdp_finish_episodes", "pomdp_controller_episodes",
     "pomdp_particle_init", "pomdp_particle_update", "pomdp_plan_particles",
     "pomdp_rollout_preferred_workspace", "pomdp_rollout_preferred", "pomdp_plan_preferred",
+    "pomdp_tree_search_workspace", "pomdp_tree_search",
 ]
 
 
@@ -122,6 +123,15 @@ class Controller(C.Structure):      # pomdp_controller
 class PlanOut(C.Structure):         # pomdp_plan_out
     _fields_ = [("q", C.c_void_p), ("visits", C.c_void_p), ("best", C.c_void_p), ("value", C.c_void_p), ("stride", C.c_int32),
                 ("reserved", C.c_int32)]
+
+
+class PlanTreeArgs(C.Structure):    # pomdp_tree_args
+    _fields_ = [("env", C.c_int32), ("depth", C.c_int32), ("params", C.c_void_p), ("root_state", C.c_void_p),
+                ("particles", C.c_void_p), ("n_roots", C.c_int64), ("n_particles", C.c_int32), ("trees_per_root", C.c_int32),
+                ("sims_per_tree", C.c_int64), ("discount", C.c_double), ("ucb_c", C.c_double), ("logn", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_uint64), ("tree_visits", C.c_void_p), ("tree_q", C.c_void_p),
+                ("n_nodes", C.c_void_p), ("sim_ret", C.c_void_p), ("sim_steps", C.c_void_p), ("sim_tree_steps", C.c_void_p),
+                ("out", PlanOut), ("seed", C.c_uint64), ("lane0", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class Returns(C.Structure):         # pomdp_returns
@@ -253,6 +263,10 @@ def lib():
     L.pomdp_rollout_preferred.argtypes = [ci, vp, vp, i64, ci, i64, ci, C.c_double, vp, vp, vp, vp, u64, u32, u64, vp, vp, vp, vp, vp, vp]
     L.pomdp_plan_preferred.restype = ci
     L.pomdp_plan_preferred.argtypes = [ci, vp, vp, i64, ci, i64, ci, C.c_double, vp, vp, vp, vp, u64, u32, u64, vp, vp, vp, vp]
+    L.pomdp_tree_search_workspace.restype = C.c_size_t
+    L.pomdp_tree_search_workspace.argtypes = [ci, vp, i64, i64, ci]
+    L.pomdp_tree_search.restype = ci
+    L.pomdp_tree_search.argtypes = [vp, u64, vp]
     L.pomdp_particle_init.restype = ci
     L.pomdp_particle_init.argtypes = [ci, vp, vp, vp, vp, vp, i64, ci, u64, u32, u64, vp]
     L.pomdp_particle_update.restype = ci

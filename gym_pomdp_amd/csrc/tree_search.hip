@@ -1,0 +1,201 @@
+// tree_search.hip — POMCP's search on the device (include/pomdp_hip.h: pomdp_tree_search): R roots x W independent UCB1 trees
+// over action-observation histories, each grown by one node per simulation with a random rollout from the new leaf, merged
+// per root (root parallelisation).  One lane per tree; the trees live in the caller's workspace (tree_pool.hip.h).
+// Part of libpomdp_hip.so; built by gym_pomdp_amd/_native.py (hipcc --offload-arch=gfx950 -O3 -std=c++17 -c, one object per file).
+#include "kernels_common.hip.h"
+#include "planner_common.hip.h"
+#include "tree_pool.hip.h"
+
+namespace pomdp {
+
+// Lane i is tree i % W of root i / W, global lane g = lane0 + i.  The simulation loop and the step loop are uniform across the
+// wave (every tree of a launch is at the same (s, k)), so the STEP key is wave-uniform; a lane whose simulation has ended idles
+// until the wave's has.  Every lane of a wave runs the lane step, as in rollout_kernel; what a lane does to its tree — the
+// selection scan, the child lookup, the backup — is the lane's own and diverges.  The simulated state lives in registers;
+// nothing is kept in scratch memory.  A rollout's policy words are the lane's ROLLOUT stream at the counter at which IT left the
+// tree (t_s + k0, per lane): one block per four rollout steps, drawn where the lane needs it.
+template <class Env>
+__global__ __launch_bounds__(BLOCK) void tree_search_kernel(const typename Env::Params p, const uint32_t *__restrict__ state,
+                                                            int64_t n_cols, int n_particles, int64_t n_trees, int trees_per_root,
+                                                            int64_t sims, int depth, double discount, double ucb_c,
+                                                            const double *__restrict__ logn, void *__restrict__ workspace,
+                                                            RngKey key0, uint32_t lane0, int32_t *__restrict__ tree_visits,
+                                                            double *__restrict__ tree_q, int32_t *__restrict__ n_nodes_out,
+                                                            int stride, double *__restrict__ sim_ret,
+                                                            int32_t *__restrict__ sim_steps, int32_t *__restrict__ sim_tree_steps)
+{
+#pragma clang fp contract(off)
+    __shared__ typename Env::Shared sh;
+    Env::stage(sh, p, (int)threadIdx.x);
+    __syncthreads();
+    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const bool in_range = i < n_trees;
+    const int64_t ic = in_range ? i : n_trees - 1;
+    const uint32_t lane = lane0 + (uint32_t)i;
+    const int64_t root = ic / trees_per_root;
+    const int n_act = Env::n_actions(p);
+    const TreeView tree = tree_view(workspace, ic, n_act, sims, depth);
+    int32_t n_nodes = 1;
+    if (in_range) tree_fresh_node(tree, 0, 0, 0);            // every search starts from an empty tree
+    const uint64_t t0 = ((uint64_t)key0.t_hi << 32) | key0.t_lo;
+#pragma unroll 1
+    for (int64_t s = 0; s < sims; ++s) {
+        const uint64_t ts = t0 + (uint64_t)s * (uint64_t)depth;
+        int64_t col = root;
+        if (n_particles > 0) {
+            const uint32_t x = stream_block(key_at(key0, ts), lane, POMDP_STREAM_TREE, 0u).x;
+            col = root * n_particles + (int64_t)__umulhi(x, (uint32_t)n_particles);
+        }
+        typename Env::State st;
+        Env::load(st, state, n_cols, (uint32_t)col);
+        double acc = 0.0, disc = 1.0;
+        int32_t h = 0, plen = 0;
+        int k = 0, d = 0, k0 = -1;                           // k0 < 0: still in the tree
+        uint4 pw = make_uint4(0, 0, 0, 0);
+        bool active = in_range;
+#pragma unroll 1
+        for (int step = 0; step < depth; ++step) {
+            const auto L = LegalOf<Env>::make(sh, p, st, false);
+            const int count = L.count;
+            active = active && !d && count > 0;
+            if (!__any(active)) break;                       // wave-uniform exit
+            int a = 0;
+            if (active) {
+                if (k0 < 0) {
+                    a = tree_select(tree, h, count, [&](int idx) { return LegalOf<Env>::pick(sh, p, st, L, idx); }, ucb_c, logn);
+                } else {
+                    const int j = step - k0;
+                    if ((j & 3) == 0) pw = stream_block(key_at(key0, ts + (uint64_t)k0), lane, POMDP_STREAM_ROLLOUT, (uint32_t)(j >> 2));
+                    const uint32_t w = (j & 3) == 0 ? pw.x : (j & 3) == 1 ? pw.y : (j & 3) == 2 ? pw.z : pw.w;
+                    a = LegalOf<Env>::pick(sh, p, st, L, (int)__umulhi(w, (uint32_t)count));
+                }
+            }
+            const RngKey key = key_at(key0, ts + (uint64_t)step);
+            typename Env::State nx = st;
+            int o2, d2;
+            typename Env::Reward rw;                         // the reward as pomdp_<env>_step writes it, then (double)
+            Env::step(sh, p, nx, a, key, lane, o2, rw, d2);
+            const double r = (double)rw;
+            if (active) {
+                st = nx; d = d2;
+                k = step + 1;
+                if (k0 < 0) {
+                    tree_push(tree, plen, h, a, r);
+                    if (!d) {
+                        bool created;
+                        h = tree_child(tree, h, a, o2, n_nodes, created);
+                        if (created) k0 = k;
+                    }
+                } else {
+                    const double term = disc * r;
+                    acc = acc + term;
+                    disc = disc * discount;
+                }
+            }
+        }
+        if (in_range) {
+            const double rt = tree_backup(tree, plen, acc, discount);
+            if (sim_ret) sim_ret[s * n_trees + i] = rt;      // kernel arguments: wave-uniform
+            if (sim_steps) sim_steps[s * n_trees + i] = k;
+            if (sim_tree_steps) sim_tree_steps[s * n_trees + i] = plen;
+        }
+    }
+    if (in_range) {
+        for (int a = 0; a < n_act; ++a) {
+            const TreeEdge e = tree.edge[a];
+            tree_visits[i * stride + a] = e.n;
+            tree_q[i * stride + a] = e.v;
+        }
+        n_nodes_out[i] = n_nodes;
+    }
+}
+
+// The merge (root parallelisation): thread r adds up the W trees of root r in ascending w — visits as integers, the
+// visit-weighted values in IEEE double from +0.0 with a separate multiply and add — and picks the best action by
+// pomdp_plan_reduce's rule.  No atomics: a root is one thread's.
+__global__ __launch_bounds__(BLOCK) void tree_merge_kernel(const int32_t *__restrict__ tree_visits, const double *__restrict__ tree_q,
+                                                           int64_t n_roots, int trees_per_root, int n_act, int stride,
+                                                           pomdp_plan_out out)
+{
+#pragma clang fp contract(off)
+    const int64_t r = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (r >= n_roots) return;
+    int b = -1;
+    double bq = 0.0;
+    for (int a = 0; a < n_act; ++a) {
+        int32_t visits = 0;
+        double total = 0.0;
+        for (int w = 0; w < trees_per_root; ++w) {
+            const int64_t k = (r * trees_per_root + w) * stride + a;
+            const int32_t n = tree_visits[k];
+            const double term = (double)n * tree_q[k];
+            total = total + term;
+            visits += n;
+        }
+        const double q = visits > 0 ? total / (double)visits : 0.0;
+        out.q[r * out.stride + a] = q;
+        out.visits[r * out.stride + a] = visits;
+        if (visits > 0 && (b < 0 || q > bq)) { b = a; bq = q; }
+    }
+    out.best[r] = b;
+    if (out.value) out.value[r] = b >= 0 ? bq : 0.0;
+}
+
+constexpr uint64_t TREE_WORKSPACE_MAX = 1ull << 46;          // refuse sizes no device holds instead of overflowing
+
+// bytes of workspace, 0 where the shape is refused; n_act: the env's action count
+static uint64_t tree_workspace_bytes(int n_act, int64_t n_trees, int64_t sims, int depth)
+{
+    if (n_act < 1 || n_act > 255 || n_trees < 0 || n_trees > (1ll << 32) || sims < 1 || depth < 0) return 0;
+    if ((sims + 1) * (int64_t)n_act > 0x7FFFFFFFll) return 0;                  // edge indices are int32
+    const unsigned __int128 total = (unsigned __int128)tree_bytes(n_act, sims, depth) * (unsigned __int128)n_trees;
+    return total > TREE_WORKSPACE_MAX ? 0 : (uint64_t)total;
+}
+
+} // namespace pomdp
+
+extern "C" {
+
+size_t pomdp_tree_search_workspace(int env, const void *params, int64_t n_trees, int64_t sims_per_tree, int depth)
+{
+    if (!params || dispatch_env(env, params, [](auto, const auto &) { return 0; })) return 0;
+    return (size_t)tree_workspace_bytes((int)env_action_count(env, params), n_trees, sims_per_tree, depth);
+}
+
+int pomdp_tree_search(const pomdp_tree_args *a, uint64_t t0, void *stream)
+{
+    if (!a || !a->params) return POMDP_E_BADARG;
+    const int rc = dispatch_env(a->env, a->params, [](auto, const auto &) { return 0; });   // POMDP_E_BADPARAMS / unknown env
+    if (rc) return rc;
+    const int n_act = (int)env_action_count(a->env, a->params);
+    const int64_t R = a->n_roots, W = a->trees_per_root, S = a->sims_per_tree;
+    if (R < 0 || R > 0x7FFFFFFF || W < 1 || S < 1 || S > 0x7FFFFFFF || a->depth < 0 || (a->lane0 & 3u) || bad_range(R * W, a->lane0) ||
+        W * S > 0x7FFFFFFFll)
+        return POMDP_E_BADARG;
+    if (!plan_out_ok(&a->out, n_act)) return POMDP_E_BADARG;                  // NULL q / visits / best, A > 255, stride < A
+    if (!a->tree_visits || !a->tree_q || !a->n_nodes || !a->logn) return POMDP_E_BADARG;
+    if (!(a->ucb_c >= 0.0) || a->ucb_c > 1.7976931348623157e308) return POMDP_E_BADARG;   // negative, NaN or infinite
+    if (a->particles) {
+        const int P = a->n_particles;
+        if (P < 4 || P > 4096 || (P & 3) || R * (int64_t)P > (1ll << 32)) return POMDP_E_BADARG;
+    } else if (a->n_particles != 0 || !a->root_state) return POMDP_E_BADARG;
+    const uint64_t need = tree_workspace_bytes(n_act, R * W, S, a->depth);
+    if (R > 0 && (need == 0 || !a->workspace || ((uintptr_t)a->workspace & 15u) || (uint64_t)a->workspace_bytes < need))
+        return POMDP_E_BADARG;
+    if (R == 0) return 0;
+    const int r2 = dispatch_env(a->env, a->params, [&](auto tag, const auto &p) {
+        using E = typename decltype(tag)::Env;
+        const int P = a->particles ? a->n_particles : 0;
+        hipLaunchKernelGGL(tree_search_kernel<E>, dim3(blocks_for(R * W)), dim3(BLOCK), 0, (hipStream_t)stream, p,
+                           a->particles ? a->particles : a->root_state, P ? R * P : R, P, R * W, (int)W, S, a->depth, a->discount,
+                           a->ucb_c, a->logn, a->workspace, make_key(a->seed, t0), a->lane0, a->tree_visits, a->tree_q, a->n_nodes,
+                           (int)a->out.stride, a->sim_ret, a->sim_steps, a->sim_tree_steps);
+        return (int)hipGetLastError();
+    });
+    if (r2) return r2;
+    hipLaunchKernelGGL(tree_merge_kernel, dim3(blocks_for(R)), dim3(BLOCK), 0, (hipStream_t)stream, a->tree_visits, a->tree_q, R,
+                       (int)W, n_act, (int)a->out.stride, a->out);
+    return (int)hipGetLastError();
+}
+
+} // extern "C"

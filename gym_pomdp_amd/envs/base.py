@@ -846,6 +846,98 @@ class BatchedEnv(compat.EnvBase):
             belief.update(a, res[0], res[1], res[2])
         return res + (p,)
 
+    def search(self, depth, sims_per_tree, trees_per_root, ucb_c, discount=None, belief=None, out=None, diagnostics=False):
+        """POMCP's tree search from the live state (pomdp_tree_search): for every lane `trees_per_root` independent UCB1 trees
+        over action-observation histories, each grown by `sims_per_tree` simulations of at most `depth` steps — UCB1 with
+        exploration constant `ucb_c` inside the tree, one new node per simulation, a uniform random rollout over
+        `_generate_legal()` from the new leaf — merged per root ON THE DEVICE.  Returns plan()'s keys {"q", "visits", "best",
+        "value"} ([R, n_actions] / [R]: visits summed and values visit-weighted over the root's trees) plus the trees' own
+        root statistics "tree_visits" int32 / "tree_q" float64 [R * trees_per_root, n_actions] and "n_nodes" int32
+        [R * trees_per_root]; `diagnostics=True` adds per-simulation "sim_ret" float64, "sim_steps" and "sim_tree_steps"
+        int32, each [sims_per_tree, R * trees_per_root].  Every float64 operation and its order are stated in
+        include/pomdp_hip.h, so the CPU restatement reproduces the result bit for bit.  Tree w of root r is global lane
+        (lane_offset + r) * trees_per_root + w: nothing depends on how the roots are sharded.  The call counter advances by
+        sims_per_tree * depth.  `ucb_c` has no default: the reference ships no planner to copy one from, and the right value
+        scales with the env's returns.
+        Without `belief` the simulations start from the TRUE states; `belief` (a ParticleBelief of this env): every
+        simulation starts from a particle of its root drawn anew (stream TREE).  `out`: the dict of an earlier call of the same
+        shape, to reuse its buffers, the workspace and the log table.  Asynchronous."""
+        import math
+        if belief is not None and not belief._shape_ok(self):
+            raise ValueError("search: the belief belongs to another env shape (%r)" % (belief,))
+        R, n_act = self._state.shape[1], self.action_space.n
+        D, S, W = int(depth), int(sims_per_tree), int(trees_per_root)
+        n = R * W
+        lane0 = self.lane_offset * W
+        if W < 1 or S < 1 or D < 0 or lane0 + n > 1 << 32:
+            raise ValueError("search: needs trees_per_root >= 1, sims_per_tree >= 1, depth >= 0 and the trees' global lanes "
+                             "(lane_offset + r) * trees_per_root + w in [0, 2^32)")
+        if lane0 % 4:
+            raise ValueError("search: lane_offset * trees_per_root must be a multiple of 4 (quad-shared Philox blocks)")
+        c = float(ucb_c)
+        if not (c >= 0.0 and math.isfinite(c)):
+            raise ValueError("search: ucb_c must be finite and >= 0, got %r" % (ucb_c,))
+        kind = _native.ENV_KIND[self.env_name]
+        if out is None:
+            dev = self.device
+            out = dict(q=torch.zeros((R, n_act), dtype=torch.float64, device=dev),
+                       visits=torch.zeros((R, n_act), dtype=torch.int32, device=dev),
+                       best=torch.empty(R, dtype=torch.int32, device=dev), value=torch.empty(R, dtype=torch.float64, device=dev),
+                       tree_visits=torch.zeros((n, n_act), dtype=torch.int32, device=dev),
+                       tree_q=torch.zeros((n, n_act), dtype=torch.float64, device=dev),
+                       n_nodes=torch.empty(n, dtype=torch.int32, device=dev))
+        elif out["q"].shape != (R, n_act) or out["tree_q"].shape != (n, n_act):
+            raise ValueError("search: `out` was built for another shape")
+        if diagnostics and ("sim_ret" not in out or out["sim_ret"].shape != (S, n)):
+            out["sim_ret"] = torch.empty((S, n), dtype=torch.float64, device=self.device)
+            out["sim_steps"] = torch.empty((S, n), dtype=torch.int32, device=self.device)
+            out["sim_tree_steps"] = torch.empty((S, n), dtype=torch.int32, device=self.device)
+        nbytes = int(self._lib.pomdp_tree_search_workspace(kind, self._params_ref, n, S, D))
+        if nbytes == 0 and n > 0:
+            raise ValueError("search: pomdp_tree_search_workspace refuses %d trees x %d simulations x depth %d" % (n, S, D))
+        ws = out.get("_workspace")
+        if ws is None or ws.numel() * 8 != nbytes:
+            ws = out["_workspace"] = torch.empty((nbytes // 16, 2), dtype=torch.float64, device=self.device)   # 16-byte units
+        logn = out.get("_logn")
+        if logn is None or logn.numel() != S + 1:
+            logn = out["_logn"] = torch.tensor([float("-inf")] + [math.log(k) for k in range(1, S + 1)], dtype=torch.float64).to(self.device)
+        diag = lambda k: out[k].data_ptr() if diagnostics else None
+        args = _native.PlanTreeArgs(
+            env=kind, depth=D, params=C.addressof(self._params), root_state=self._state.data_ptr(),
+            particles=None if belief is None else belief.particles.data_ptr(), n_roots=R,
+            n_particles=0 if belief is None else belief.n_particles, trees_per_root=W, sims_per_tree=S,
+            discount=float(self._discount if discount is None else discount), ucb_c=c, logn=logn.data_ptr(),
+            workspace=ws.data_ptr(), workspace_bytes=nbytes, tree_visits=out["tree_visits"].data_ptr(),
+            tree_q=out["tree_q"].data_ptr(), n_nodes=out["n_nodes"].data_ptr(), sim_ret=diag("sim_ret"),
+            sim_steps=diag("sim_steps"), sim_tree_steps=diag("sim_tree_steps"),
+            out=_native.PlanOut(q=out["q"].data_ptr(), visits=out["visits"].data_ptr(), best=out["best"].data_ptr(),
+                                value=out["value"].data_ptr(), stride=n_act, reserved=0),
+            seed=self._seed, lane0=lane0, reserved=0)
+        t0 = self._t
+        self._t += S * D
+        with torch.cuda.device(self.device):
+            rc = self._lib.pomdp_tree_search(C.byref(args), t0, self._stream())
+            _native.check(rc, "pomdp_tree_search")
+        return out
+
+    def search_step(self, depth, sims_per_tree, trees_per_root, ucb_c, discount=None, belief=None, out=None, diagnostics=False):
+        """One REAL step of every lane, searched: search() from the live state (or from `belief`'s particles), then step(best)
+        and, with `belief`, belief.update(best, ob, reward, done) — what plan_step() is to plan().  Returns (ob, reward, done,
+        info, search dict).  A lane whose search took no step (best == -1) is handed -1, which step() counts as an invalid
+        action.  With `belief` it needs auto_reset=False; the caller restarts ended lanes as after plan_step()."""
+        if belief is not None and self._auto_reset:
+            raise ValueError("search_step(belief=...) needs auto_reset=False: restart ended lanes with env.reset(where=done) and "
+                             "belief.reset(ob, where=done)")
+        p = self.search(depth, sims_per_tree, trees_per_root, ucb_c, discount, belief=belief, out=out, diagnostics=diagnostics)
+        a = p["best"]
+        if self.batch_size == 1:
+            a = int(a.item())
+            assert a >= 0, "search_step: no simulation took a step"
+        res = self.step(a)
+        if belief is not None:
+            belief.update(a, res[0], res[1], res[2])
+        return res + (p,)
+
     def particle_belief(self, n_particles=256, seed=None):
         """A ParticleBelief of n_particles particles per lane of this env (gym_pomdp_amd.particles); call its reset(ob) with
         the observation of this env's reset() before planning from it."""

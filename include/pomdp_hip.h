@@ -65,6 +65,7 @@
 #ifndef POMDP_HIP_H
 #define POMDP_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -89,7 +90,7 @@ enum {
 /* id of the word streams of one (seed, lane, t) */
 enum { POMDP_STREAM_STEP = 0, POMDP_STREAM_RESET = 1, POMDP_STREAM_STEP_SPACE = 2,
        POMDP_STREAM_RESET_SPACE = 3, POMDP_STREAM_ACTION = 4, POMDP_STREAM_ROLLOUT = 5, POMDP_STREAM_NEXT = 6,
-       POMDP_STREAM_STEP_LO = 7, POMDP_STREAM_PARTICLE = 8 };
+       POMDP_STREAM_STEP_LO = 7, POMDP_STREAM_PARTICLE = 8, POMDP_STREAM_TREE = 9 };
 
 /* env kinds for the generic entry points */
 enum { POMDP_ENV_ROCK = 0, POMDP_ENV_TAG = 1, POMDP_ENV_BATTLESHIP = 2, POMDP_ENV_TIGER = 3, POMDP_ENV_NETWORK = 4 };
@@ -529,7 +530,9 @@ int pomdp_rollout(int env, const void *params, const uint32_t *root_state, int64
  * rollout per real step") ------------------------------------------------------------------------------------------
  * What the reference's hooks exist to be driven for (rock.py:243-245 _set_state, 266-291 _get_init_state /
  * _generate_legal, 115 _discount; readme.md:38-41 credits POMCP): the caller simulates from each root, turns the
- * simulations into action values and takes the best action in the real env.  Per root r, over its sims_per_root
+ * simulations into action values and takes the best action in the real env.  This planner is FLAT Monte Carlo — independent
+ * rollouts, no search tree, no UCB: nothing simulation s learns steers simulation s + 1; POMCP's search itself is
+ * pomdp_tree_search (below).  Per root r, over its sims_per_root
  * simulations (simulation s of root r is lane r * sims_per_root + s of pomdp_rollout's outputs):
  *     visits[r][a] = the number of simulations whose first action was a
  *     q[r][a]      = (sum of their returns) / visits[r][a]            0.0 where visits == 0
@@ -564,7 +567,7 @@ int pomdp_plan(int env, const void *params, const uint32_t *root_state, int64_t 
                int depth, double discount, int flags, uint64_t seed, uint32_t lane0, uint64_t t0,
                double *sim_ret, int32_t *sim_first_action, const pomdp_plan_out *out, void *stream);
 
-/* ---- particle beliefs: the belief a POMCP-style planner keeps per real episode ---------------------------------------
+/* ---- particle beliefs: the belief a POMCP planner keeps per real episode ---------------------------------------------
  * pomdp_plan plans from the TRUE state of each root (flat Monte Carlo with the hidden state known).  A planner that does not
  * know the hidden state keeps a set of P particles per root instead: after each real step it keeps the particles that, under
  * the real action, reproduce the real observation, redraws the others from them, and plans from the particles.
@@ -779,6 +782,88 @@ int pomdp_plan_preferred(int env, const void *params, const uint32_t *state, int
                          int64_t sims_per_root, int depth, double discount, const pomdp_rock_belief *b, const pomdp_history *h,
                          const int32_t *prev_ob, void *workspace, uint64_t seed, uint32_t lane0, uint64_t t0, double *sim_ret,
                          int32_t *sim_first_action, const pomdp_plan_out *out, void *stream);
+
+/* ---- POMCP's tree search (added to ABI 15: new entry points only, nothing existing changes) ------------------------------
+ * pomdp_plan is flat Monte Carlo: independent rollouts, the mean return by first action.  This is the search POMCP (Silver &
+ * Veness, NIPS 2010) builds from the same hooks: a UCB1 tree over action-observation histories, grown by one node per
+ * simulation, with a uniform random rollout from each new leaf; many trees side by side, and several independent trees per
+ * root merged at the root (root parallelisation: the simulations of one tree are sequential by nature).
+ *
+ * Lanes.  A search runs R = n_roots roots x W = trees_per_root trees per root; each tree runs S = sims_per_tree simulations of
+ *   at most D = depth steps.  Tree w of root r is global lane g = lane0 + r * W + w; lane0 = lane_offset * W for a shard of
+ *   roots starting at root lane_offset, and whole roots never straddle a shard, so results do not depend on sharding.
+ *   lane0 % 4 == 0 (RockSample's STEP blocks are shared by global lanes 4 q .. 4 q + 3), lane0 + R * W <= 2^32, W >= 1,
+ *   S >= 1, D >= 0; also W * S <= 2^31 - 1 (merged visit counts are int32) and (S + 1) * A <= 2^31 - 1.
+ * Call counters.  Simulation s of every tree runs at t_s = t0 + s * D; its step k (k = 0 .. D - 1, counted from the root) draws
+ *   the env's randomness from stream STEP at (seed, g, t_s + k): exactly what pomdp_<env>_step at that lane and counter draws,
+ *   with no auto-reset.  All trees of a launch are at the same (s, k) at the same time, so the counter is uniform across a
+ *   wave.  The env's call counter advances by S * D per search; counters wrap mod 2^64 as everywhere else.
+ * Start state.  Without particles (particles == NULL, n_particles == 0): column r of root_state (uint32 [words][R]), the true
+ *   state, as in pomdp_plan.  With particles (P = n_particles per root, uint32 [words][R * P], column r * P + j: the layout
+ *   and the P rules of pomdp_plan_particles; root_state is ignored): particle j = (x * P) >> 32 of root r, x = word 0 of block 0
+ *   of stream TREE at (seed, g, t_s) (counter (g, t_s lo, t_s hi, POMDP_STREAM_TREE << 24), as the PARTICLE words are built).
+ * A tree is a pool of at most S + 1 nodes; node 0 is the root history.  Every node keeps N(h,a) (int32) and V(h,a) (double) for
+ *   each of the env's A actions, all zero at creation.  Children are found by (action, observation), both full int32.  Node
+ *   indices are handed out in creation order.  Every search starts from an empty tree (no reuse after the real step).
+ * Simulation s, with h = node 0, k = 0 and mode = tree:
+ *   1. If k == D, stop.  L = _generate_legal() of the simulated state, in the env's list order (pomdp_legal_actions).  If L is
+ *      empty, stop.
+ *   2. Tree mode: if some a in L has N(h,a) == 0, take the first such in list order.  Otherwise let Nh = sum of N(h,a) over all
+ *      A actions and take the first maximum, in list order, of u(a) = V(h,a) + c * sqrt(logn[Nh] / (double)N(h,a)), c = ucb_c:
+ *      one IEEE division, one square root, one multiply and one add, none fused.  logn is the caller's device table, double
+ *      [S + 1], logn[n] = log(n) computed on the host (entry 0 is never read): the device never calls log.
+ *   3. Rollout mode: a = L[(x * len(L)) >> 32], x = word j of stream ROLLOUT at (seed, g, t_s + k0), k0 = the step index at
+ *      which this simulation left the tree, j = k - k0.  The rollout phase draws word for word what a pomdp_rollout simulation
+ *      of depth D - k0 from the leaf at t0' = t_s + k0 draws.
+ *   4. (o, r, done) = step(a), then k += 1; r is the reward as pomdp_<env>_step writes it (int32 or float), converted to double.
+ *      (Network's pomdp_rollout accumulates its reward before the rounding to float: a search's rollout return can differ from
+ *      pomdp_rollout's there in the last bits; every other env's rewards are integers.)  Tree mode: push (h, a, r) on the
+ *      path.  Rollout mode: acc += disc * r; disc *= discount — separate multiply and add, from acc = 0, disc = 1 at the leaf.
+ *   5. If done, stop.
+ *   6. Tree mode: if child (h, a, o) exists it becomes h; otherwise it is created — whatever depth remains — and the mode
+ *      becomes rollout (k0 = k).
+ * Backup.  Rt = acc (0.0 if there was no rollout); walking the path from its deepest entry to the root, for each entry:
+ *   Rt = r + discount * Rt (multiply, then add);  N(h,a) += 1;  V(h,a) = V(h,a) + (Rt - V(h,a)) / (double)N(h,a).
+ *   The final Rt is sim_ret[s].
+ * Per-tree outputs (device; tree i = r * W + w): tree_visits int32 and tree_q double, both [R * W][out.stride]: node 0's N and
+ *   V; n_nodes int32 [R * W].  Diagnostics, each may be NULL: sim_ret double [S][R * W], sim_steps int32 [S][R * W] (steps
+ *   taken), sim_tree_steps int32 [S][R * W] (of them in tree mode).
+ * Merge per root, into `out`:  visits[r][a] = sum over w of N_w(0,a);  q[r][a] = (sum over w of (double)N_w(0,a) * V_w(0,a))
+ *   / visits — the sum from +0.0 in ascending w, separate multiply and add — and 0.0 where visits == 0;  best / value by
+ *   pomdp_plan_reduce's rule: the largest q among the visited actions, the lowest index on ties, -1 / 0.0 if none.
+ * workspace: device, 16-byte aligned, at least pomdp_tree_search_workspace bytes (0 = the shape is refused) for R * W trees:
+ *   the node pools, child links and path stacks.  It need not be initialised; its contents afterwards are unspecified.
+ * Everything is checked before anything is enqueued (POMDP_E_BADARG / POMDP_E_BADPARAMS): NULL pointers, A > 255, out.stride <
+ *   A, a workspace that is too small, the lane rules, ucb_c negative or not finite, P outside pomdp_plan_particles' rules.
+ *   n_roots == 0 returns 0 and launches nothing.  Two launches: the search (one lane per tree) and the merge. */
+typedef struct pomdp_tree_args {
+    int32_t env;              /* POMDP_ENV_* */
+    int32_t depth;            /* D */
+    const void *params;       /* the env's params struct */
+    const uint32_t *root_state;   /* device; read when particles == NULL */
+    const uint32_t *particles;    /* device, or NULL: plan from the true states */
+    int64_t n_roots;          /* R */
+    int32_t n_particles;      /* P; 0 with particles == NULL */
+    int32_t trees_per_root;   /* W */
+    int64_t sims_per_tree;    /* S */
+    double  discount;
+    double  ucb_c;
+    const double *logn;       /* device double [S + 1] */
+    void    *workspace;       /* device */
+    uint64_t workspace_bytes;
+    int32_t *tree_visits;     /* device int32  [R * W][out.stride] */
+    double  *tree_q;          /* device double [R * W][out.stride] */
+    int32_t *n_nodes;         /* device int32  [R * W] */
+    double  *sim_ret;         /* device double [S][R * W], or NULL */
+    int32_t *sim_steps;       /* device int32  [S][R * W], or NULL */
+    int32_t *sim_tree_steps;  /* device int32  [S][R * W], or NULL */
+    pomdp_plan_out out;       /* the merged result */
+    uint64_t seed;
+    uint32_t lane0;
+    uint32_t reserved;
+} pomdp_tree_args;
+size_t pomdp_tree_search_workspace(int env, const void *params, int64_t n_trees, int64_t sims_per_tree, int depth);
+int pomdp_tree_search(const pomdp_tree_args *a, uint64_t t0, void *stream);
 
 int         pomdp_abi_version(void);
 const char *pomdp_error_string(int code);

@@ -1,0 +1,89 @@
+#!/usr/bin/env python
+"""GPU box: search() against plan() at an equal simulation budget in one process, HIP events after warm-up — BASELINE.json
+configs[4]'s shape by default: RockSample(15,15), 2048 roots, search with 16 trees per root x 64 simulations of depth 64
+against plan(64, 1024), both 1024 simulations per root, from the true states and from 256 particles per root.  The roots
+are a few real steps into their episodes.  One JSON line (profiles/r24_tree_search_timing.json), with the search kernel's
+resources (tools/kernel_resources.py; compiled on the spot, no GPU work).  Run it under `timeout`."""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.join(REPO, "tools"))
+
+
+def timed(fn, reps):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ms = []
+    for _ in range(reps):
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    ms.sort()
+    return ms[len(ms) // 2], ms[0], ms[-1]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--board", type=int, default=15)
+    ap.add_argument("--rocks", type=int, default=15)
+    ap.add_argument("--roots", type=int, default=2048)
+    ap.add_argument("--trees", type=int, default=16)
+    ap.add_argument("--sims", type=int, default=64)
+    ap.add_argument("--depth", type=int, default=64)
+    ap.add_argument("--ucb-c", type=float, default=20.0)
+    ap.add_argument("--particles", type=int, default=256)
+    ap.add_argument("--prep", type=int, default=8)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--no-resources", action="store_true")
+    args = ap.parse_args()
+    import gym_pomdp_amd as gpa
+    e = gpa.make("Rock-v0", board_size=args.board, num_rocks=args.rocks, batch_size=args.roots, auto_reset=False, seed=1)
+    ob = e.reset()
+    bel = e.particle_belief(args.particles)
+    bel.reset(ob)
+    for _ in range(args.prep):
+        a = e.synthetic_actions()
+        ob, rew, done, _ = e.step(a)
+        bel.update(a, ob)
+    budget = args.trees * args.sims
+    res = dict(tool="gpu_tree_search_timing", env="RockSample(%d,%d)" % (args.board, args.rocks), roots=args.roots,
+               trees_per_root=args.trees, sims_per_tree=args.sims, depth=args.depth, ucb_c=args.ucb_c, particles=args.particles,
+               sims_per_root=budget, reps=args.reps, warmup=args.warmup, device=torch.cuda.get_device_name(0))
+    for name, b in (("true", None), ("particles", bel)):
+        s_out = e.search(args.depth, args.sims, args.trees, args.ucb_c, belief=b, diagnostics=True)
+        p_out = e.plan(args.depth, budget, belief=b)
+        search = lambda: e.search(args.depth, args.sims, args.trees, args.ucb_c, belief=b, out=s_out, diagnostics=True)
+        plan = lambda: e.plan(args.depth, budget, belief=b, out=p_out)
+        for what, fn in (("search", search), ("plan", plan)):
+            for _ in range(args.warmup):
+                fn()
+            torch.cuda.synchronize()
+            med, lo, hi = timed(fn, args.reps)
+            res["%s_%s_ms" % (name, what)] = round(med, 4)
+            res["%s_%s_min_ms" % (name, what)] = round(lo, 4)
+            res["%s_%s_max_ms" % (name, what)] = round(hi, 4)
+        res["%s_ratio" % name] = round(res["%s_search_ms" % name] / res["%s_plan_ms" % name], 3)
+        steps = int(s_out["sim_steps"].sum().item())
+        res["%s_search_sim_steps" % name] = steps
+        res["%s_search_tree_steps" % name] = int(s_out["sim_tree_steps"].sum().item())
+        res["%s_search_steps_per_s" % name] = round(steps / (res["%s_search_ms" % name] * 1e-3), 1)
+        res["%s_search_mean_nodes" % name] = round(float(s_out["n_nodes"].double().mean().item()), 2)
+        res["%s_best_agree" % name] = round(float((s_out["best"] == p_out["best"]).double().mean().item()), 4)
+    res["workspace_bytes"] = int(s_out["_workspace"].numel() * 8)
+    if not args.no_resources:
+        import kernel_resources as kr
+        want = "tree_search_kernel<RockEnv<%d, false> >" % (1 if args.rocks <= 12 else 2)
+        res["resources"] = [r for r in kr.collect(units=["tree_search.hip"]) if r["kernel"] in (want, "tree_merge_kernel")]
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
