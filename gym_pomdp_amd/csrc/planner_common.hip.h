@@ -7,6 +7,9 @@
 
 namespace pomdp {
 
+// envs whose _generate_preferred is a policy of its own (RockSample's heuristic, Tag); for the others it is the legal list
+template <class Env> struct has_policy : std::integral_constant<bool, Env::HAS_ROCKS || std::is_same<Env, TagEnv>::value> {};
+
 // envs whose _generate_preferred reads extra LDS tables fill them with Env::stage_policy
 template <class Env, class = void> struct HasPolicyTables : std::false_type {};
 template <class Env> struct HasPolicyTables<Env, std::void_t<decltype(&Env::stage_policy)>> : std::true_type {};

@@ -7,9 +7,6 @@
 
 namespace pomdp {
 
-// envs whose _generate_preferred is a policy of its own (RockSample's heuristic, Tag); for the others it is the legal list
-template <class Env> struct has_policy : std::integral_constant<bool, Env::HAS_ROCKS || std::is_same<Env, TagEnv>::value> {};
-
 // rollout_kernel under the env's preferred-action policy (include/pomdp_hip.h: pomdp_rollout_preferred): the same lanes,
 // words, step and return, with the list of step k being _generate_preferred(history) of the SIMULATION's own statistics and
 // history.  Lane i belongs to root r = i / sims_per_root and starts from state column i / sims_per_col (true states:

@@ -1,6 +1,7 @@
 // tree_pool.hip.h — the node pool of one search tree (include/pomdp_hip.h: pomdp_tree_search): UCB1 selection, child lookup /
 // insert, the path stack and the backup.  __host__ __device__ and free of device builtins, so that the same text runs inside
-// tree_search_kernel and in a stand-alone host program (which is how its bounds were checked before it first ran on a GPU).
+// the search kernels (tree_search.hip, tree_search_preferred.hip) and in a stand-alone host program (which is how its bounds
+// were checked before it first ran on a GPU).
 //
 // Layout: a tree owns three consecutive arrays of the caller's workspace,
 //   edge [S + 1][A]   16 B   {V(h,a) double, N(h,a) int32, first child of (h,a) int32}: what selection reads per legal action is ONE
@@ -73,14 +74,16 @@ static POMDP_TREE_HD void tree_fresh_node(const TreeView &t, int32_t h, int32_t 
 }
 
 // Selection at node h over the legal list (count entries, pick(i) its i-th): the first entry with N == 0, else the first
-// maximum of V + c * sqrt(logn[Nh] / N) — one division, one square root, one multiply, one add, none fused.
+// maximum of V + c * sqrt(logn[Nh] / N) — one division, one square root, one multiply, one add, none fused.  logn has
+// nh_max + 1 entries: S + 1 for a search without priors, S + 1 + A * prior_n with them (tree_node_priors).
 template <class Pick>
-static POMDP_TREE_HD int32_t tree_select(const TreeView &t, int32_t h, int count, Pick pick, double ucb_c, const double *logn)
+static POMDP_TREE_HD int32_t tree_select_clamped(const TreeView &t, int32_t h, int count, Pick pick, double ucb_c, const double *logn,
+                                                 int32_t nh_max)
 {
 #pragma clang fp contract(off)
     const int32_t hc = tree_clamp_node(t, h);
     int32_t nh = t.node[hc].visits;
-    nh = nh < 0 ? 0 : (nh > t.d.S ? t.d.S : nh);             // logn has S + 1 entries
+    nh = nh < 0 ? 0 : (nh > nh_max ? nh_max : nh);
     const double ln = logn[nh];
     int32_t fresh = -1, best = -1;
     double bu = 0.0;
@@ -99,7 +102,31 @@ static POMDP_TREE_HD int32_t tree_select(const TreeView &t, int32_t h, int count
     }
     return fresh >= 0 ? fresh : best;
 }
+template <class Pick>
+static POMDP_TREE_HD int32_t tree_select(const TreeView &t, int32_t h, int count, Pick pick, double ucb_c, const double *logn)
+{
+    return tree_select_clamped(t, h, count, pick, ucb_c, logn, t.d.S);   // logn has S + 1 entries
+}
 
+// Node priors (pomdp_tree_search_preferred), the second half of a node's creation where the search sets them: the edges of
+// node h start at N = prior_n, V = prior_v for the actions a with
+// in(a) and at N = V = 0 for the others, no child anywhere, and the node's visits at prior_n * |{a : in(a)}| (prior_n <=
+// 65535 and A <= 255: below 2^24).  For a node that has no child yet: the node created last, or node 0 of an empty tree.
+// Stores only — the node's observation and sibling link stay as its creation wrote them.
+template <class In>
+static POMDP_TREE_HD void tree_node_priors(const TreeView &t, int32_t h, In in, int32_t prior_n, double prior_v)
+{
+    const int32_t hc = tree_clamp_node(t, h);
+    const int32_t pn = prior_n < 0 ? 0 : (prior_n > 65535 ? 65535 : prior_n);
+    int32_t listed = 0;
+    for (int32_t a = 0; a < t.d.A; ++a) {
+        const bool on = in(a);
+        TreeEdge e; e.v = on ? prior_v : 0.0; e.n = on ? pn : 0; e.child = 0;
+        t.edge[(int64_t)hc * t.d.A + a] = e;
+        listed += (int32_t)on;
+    }
+    t.node[hc].visits = pn * listed;
+}
 // the child of (h, a) under observation ob; created — as node n_nodes, whatever depth remains — when there is none.
 // -> its index; `created` tells which.  A full pool (impossible: one insert per simulation) hands back the root.
 static POMDP_TREE_HD int32_t tree_child(const TreeView &t, int32_t h, int32_t a, int32_t ob, int32_t &n_nodes, bool &created)

@@ -152,17 +152,9 @@ static uint64_t tree_workspace_bytes(int n_act, int64_t n_trees, int64_t sims, i
     return total > TREE_WORKSPACE_MAX ? 0 : (uint64_t)total;
 }
 
-} // namespace pomdp
-
-extern "C" {
-
-size_t pomdp_tree_search_workspace(int env, const void *params, int64_t n_trees, int64_t sims_per_tree, int depth)
-{
-    if (!params || dispatch_env(env, params, [](auto, const auto &) { return 0; })) return 0;
-    return (size_t)tree_workspace_bytes((int)env_action_count(env, params), n_trees, sims_per_tree, depth);
-}
-
-int pomdp_tree_search(const pomdp_tree_args *a, uint64_t t0, void *stream)
+// pomdp_tree_search's argument checks, shared with pomdp_tree_search_preferred (tree_search_preferred.hip): -> 0 and the env's
+// action count, or the error to return; nothing is enqueued
+int tree_check_args(const pomdp_tree_args *a, int *n_act_out)
 {
     if (!a || !a->params) return POMDP_E_BADARG;
     const int rc = dispatch_env(a->env, a->params, [](auto, const auto &) { return 0; });   // POMDP_E_BADPARAMS / unknown env
@@ -182,6 +174,34 @@ int pomdp_tree_search(const pomdp_tree_args *a, uint64_t t0, void *stream)
     const uint64_t need = tree_workspace_bytes(n_act, R * W, S, a->depth);
     if (R > 0 && (need == 0 || !a->workspace || ((uintptr_t)a->workspace & 15u) || (uint64_t)a->workspace_bytes < need))
         return POMDP_E_BADARG;
+    *n_act_out = n_act;
+    return 0;
+}
+
+// the merge launch over the trees' root statistics a search kernel left in a->tree_visits / a->tree_q
+int launch_tree_merge(const pomdp_tree_args *a, int n_act, void *stream)
+{
+    hipLaunchKernelGGL(tree_merge_kernel, dim3(blocks_for(a->n_roots)), dim3(BLOCK), 0, (hipStream_t)stream, a->tree_visits, a->tree_q,
+                       a->n_roots, (int)a->trees_per_root, n_act, (int)a->out.stride, a->out);
+    return (int)hipGetLastError();
+}
+
+} // namespace pomdp
+
+extern "C" {
+
+size_t pomdp_tree_search_workspace(int env, const void *params, int64_t n_trees, int64_t sims_per_tree, int depth)
+{
+    if (!params || dispatch_env(env, params, [](auto, const auto &) { return 0; })) return 0;
+    return (size_t)tree_workspace_bytes((int)env_action_count(env, params), n_trees, sims_per_tree, depth);
+}
+
+int pomdp_tree_search(const pomdp_tree_args *a, uint64_t t0, void *stream)
+{
+    int n_act = 0;
+    const int rc = tree_check_args(a, &n_act);
+    if (rc) return rc;
+    const int64_t R = a->n_roots, W = a->trees_per_root, S = a->sims_per_tree;
     if (R == 0) return 0;
     const int r2 = dispatch_env(a->env, a->params, [&](auto tag, const auto &p) {
         using E = typename decltype(tag)::Env;
@@ -193,9 +213,7 @@ int pomdp_tree_search(const pomdp_tree_args *a, uint64_t t0, void *stream)
         return (int)hipGetLastError();
     });
     if (r2) return r2;
-    hipLaunchKernelGGL(tree_merge_kernel, dim3(blocks_for(R)), dim3(BLOCK), 0, (hipStream_t)stream, a->tree_visits, a->tree_q, R,
-                       (int)W, n_act, (int)a->out.stride, a->out);
-    return (int)hipGetLastError();
+    return launch_tree_merge(a, n_act, stream);
 }
 
 } // extern "C"

@@ -846,7 +846,8 @@ class BatchedEnv(compat.EnvBase):
             belief.update(a, res[0], res[1], res[2])
         return res + (p,)
 
-    def search(self, depth, sims_per_tree, trees_per_root, ucb_c, discount=None, belief=None, out=None, diagnostics=False):
+    def search(self, depth, sims_per_tree, trees_per_root, ucb_c, discount=None, belief=None, out=None, diagnostics=False,
+               policy="uniform", history=None, prior_n=0, prior_v=0.0):
         """POMCP's tree search from the live state (pomdp_tree_search): for every lane `trees_per_root` independent UCB1 trees
         over action-observation histories, each grown by `sims_per_tree` simulations of at most `depth` steps — UCB1 with
         exploration constant `ucb_c` inside the tree, one new node per simulation, a uniform random rollout over
@@ -861,8 +862,23 @@ class BatchedEnv(compat.EnvBase):
         scales with the env's returns.
         Without `belief` the simulations start from the TRUE states; `belief` (a ParticleBelief of this env): every
         simulation starts from a particle of its root drawn anew (stream TREE).  `out`: the dict of an earlier call of the same
-        shape, to reuse its buffers, the workspace and the log table.  Asynchronous."""
+        shape, to reuse its buffers, the workspaces and the log table.  Asynchronous.
+        `policy="preferred"` with `history=` (an unbounded History of this env): POMCP as it runs on RockSample and Tag
+        (pomdp_tree_search_preferred).  Every simulation starts from the live lanes' side statistics and history, keeps its own
+        copies of them through the tree and the rollout, and rolls out under `_generate_preferred(history)`; nothing of the
+        env or the History is written.  `prior_n` > 0 (at most 65535) with `prior_v`: a new node's preferred actions start with
+        N = prior_n and V = prior_v ("smart tree"), and "tree_visits" / "visits" include those counts.  The envs whose
+        preferred list is the legal list, and a RockSample env built without use_heuristic, run the uniform search; with
+        prior_n > 0 they raise ValueError: a uniform prior over the legal list steers nothing."""
         import math
+        preferred = self._preferred_policy("search", policy, history, False, None)
+        prior_n, prior_v = int(prior_n), float(prior_v)
+        if prior_n < 0 or prior_n > 65535 or not math.isfinite(prior_v):
+            raise ValueError("search: needs 0 <= prior_n <= 65535 and a finite prior_v, got %r, %r" % (prior_n, prior_v))
+        preferred = preferred and self.env_name in ("rock", "tag")
+        if prior_n > 0 and not preferred:
+            raise ValueError("search: prior_n > 0 needs policy='preferred' on an env with a preferred-action policy of its own "
+                             "(RockSample with use_heuristic=True, Tag): a uniform prior over the legal list steers nothing")
         if belief is not None and not belief._shape_ok(self):
             raise ValueError("search: the belief belongs to another env shape (%r)" % (belief,))
         R, n_act = self._state.shape[1], self.action_space.n
@@ -898,9 +914,12 @@ class BatchedEnv(compat.EnvBase):
         ws = out.get("_workspace")
         if ws is None or ws.numel() * 8 != nbytes:
             ws = out["_workspace"] = torch.empty((nbytes // 16, 2), dtype=torch.float64, device=self.device)   # 16-byte units
+        n_log = S + 1 + n_act * prior_n                      # Nh counts the priors
+        if prior_n > 0 and W * (n_log - 1) > 0x7FFFFFFF:
+            raise ValueError("search: trees_per_root * (sims_per_tree + n_actions * prior_n) must stay below 2^31 (merged visits)")
         logn = out.get("_logn")
-        if logn is None or logn.numel() != S + 1:
-            logn = out["_logn"] = torch.tensor([float("-inf")] + [math.log(k) for k in range(1, S + 1)], dtype=torch.float64).to(self.device)
+        if logn is None or logn.numel() != n_log:
+            logn = out["_logn"] = torch.tensor([float("-inf")] + [math.log(k) for k in range(1, n_log)], dtype=torch.float64).to(self.device)
         diag = lambda k: out[k].data_ptr() if diagnostics else None
         args = _native.PlanTreeArgs(
             env=kind, depth=D, params=C.addressof(self._params), root_state=self._state.data_ptr(),
@@ -915,25 +934,53 @@ class BatchedEnv(compat.EnvBase):
             seed=self._seed, lane0=lane0, reserved=0)
         t0 = self._t
         self._t += S * D
+        if preferred:
+            rock = self.env_name == "rock"
+            pbytes = int(self._lib.pomdp_tree_search_preferred_workspace(kind, self._params_ref, n))
+            pws = out.get("_policy_workspace")
+            if pws is None or pws.numel() * 8 != pbytes:
+                pws = out["_policy_workspace"] = torch.empty((pbytes // 16, 2), dtype=torch.float64, device=self.device)
+            pol = _native.PlanTreePolicy(
+                belief=C.addressof(self._tracker.ptrs) if rock else None, history=C.addressof(history._ptrs),
+                prev_ob=history.prev_ob.data_ptr() if rock else None, workspace=pws.data_ptr() if pbytes else None,
+                workspace_bytes=pbytes, prior_n=prior_n, reserved=0, prior_v=prior_v)
+            with torch.cuda.device(self.device):
+                rc = self._lib.pomdp_tree_search_preferred(C.byref(args), C.byref(pol), t0, self._stream())
+                _native.check(rc, "pomdp_tree_search_preferred")
+            return out
         with torch.cuda.device(self.device):
             rc = self._lib.pomdp_tree_search(C.byref(args), t0, self._stream())
             _native.check(rc, "pomdp_tree_search")
         return out
 
-    def search_step(self, depth, sims_per_tree, trees_per_root, ucb_c, discount=None, belief=None, out=None, diagnostics=False):
+    def search_step(self, depth, sims_per_tree, trees_per_root, ucb_c, discount=None, belief=None, out=None, diagnostics=False,
+                    policy="uniform", history=None, prior_n=0, prior_v=0.0):
         """One REAL step of every lane, searched: search() from the live state (or from `belief`'s particles), then step(best)
         and, with `belief`, belief.update(best, ob, reward, done) — what plan_step() is to plan().  Returns (ob, reward, done,
         info, search dict).  A lane whose search took no step (best == -1) is handed -1, which step() counts as an invalid
-        action.  With `belief` it needs auto_reset=False; the caller restarts ended lanes as after plan_step()."""
+        action.  With `belief` it needs auto_reset=False; the caller restarts ended lanes as after plan_step().
+        `policy="preferred"` with `history=` (and `prior_n`, `prior_v`): search() under the env's preferred-action policy, then
+        the agent's knowledge follows the real step exactly as in plan_step(): step() updates RockSample's side statistics, the
+        transition (history.prev_ob, best, reward, ob, done) is appended to `history` and history.prev_ob becomes ob — next to
+        belief.update(...) when `belief` is given.  Needs auto_reset=False for the same reason."""
         if belief is not None and self._auto_reset:
             raise ValueError("search_step(belief=...) needs auto_reset=False: restart ended lanes with env.reset(where=done) and "
                              "belief.reset(ob, where=done)")
-        p = self.search(depth, sims_per_tree, trees_per_root, ucb_c, discount, belief=belief, out=out, diagnostics=diagnostics)
+        if policy == "preferred" and self._auto_reset:
+            raise ValueError("search_step(policy='preferred') needs auto_reset=False: restart ended lanes with "
+                             "env.reset(where=done) and history.clear(where=done)")
+        p = self.search(depth, sims_per_tree, trees_per_root, ucb_c, discount, belief=belief, out=out, diagnostics=diagnostics,
+                        policy=policy, history=history, prior_n=prior_n, prior_v=prior_v)
         a = p["best"]
         if self.batch_size == 1:
             a = int(a.item())
             assert a >= 0, "search_step: no simulation took a step"
         res = self.step(a)
+        if history is not None:
+            from ..history import Transition
+            history.append(Transition(history.prev_ob, a, res[1], res[0], res[2]), auto_reset=False)
+            if history.prev_ob is not None:
+                history.prev_ob.copy_(torch.as_tensor(res[0], device=self.device).to(torch.int32).reshape(self.batch_size))
         if belief is not None:
             belief.update(a, res[0], res[1], res[2])
         return res + (p,)

@@ -865,6 +865,57 @@ typedef struct pomdp_tree_args {
 size_t pomdp_tree_search_workspace(int env, const void *params, int64_t n_trees, int64_t sims_per_tree, int depth);
 int pomdp_tree_search(const pomdp_tree_args *a, uint64_t t0, void *stream);
 
+/* ---- the search under the env's preferred-action policy (added to ABI 15: new entry points only, nothing existing changes) --
+ * pomdp_tree_search as POMCP runs it on RockSample and Tag: rollouts pick from _generate_preferred(history) and a new node's
+ * preferred actions start with a count and a value ("smart tree").  `a` means what it means for pomdp_tree_search, except that
+ * a->logn has S + 1 + A * prior_n entries (logn[n] = log(n), entry 0 never read).  Stated as the differences from that
+ * contract's numbered steps; every float64 operation is one of its own (no new one is added: a prior is a stored value).
+ * Private policy inputs.  At the start of EVERY simulation the lane takes root r's policy inputs, read-only and indexed by real
+ *   root r < R as for pomdp_rollout_preferred: size, last_action, last_ob of pol->history for every env; for RockSample also
+ *   check_ok (pol->belief), move_ok, prev_ob (pol->prev_ob, int32 [R]) and per rock count, measured, lkv, lkw (pol->belief),
+ *   total_sample, total_move (pol->history).  After every executed step 4, in tree mode and in rollout mode alike, the lane
+ *   updates its own copies exactly as a simulation of pomdp_rollout_preferred does after its step (its item 4): the history
+ *   append and, for an executed CHECK, the two history sums (the prev_ob == BAD rule included) and, with ob != 0 and not done,
+ *   the side statistics in pomdp_rock_belief_update's float64 operations and order — one subtraction 1 - eff; lkv *= eff and
+ *   lkw *= (1 - eff) for GOOD, the other way round for BAD; prob_valuable = (.5 * lkv) / ((.5 * lkv) + (.5 * lkw)): two more
+ *   multiplies, one add, one division, none fused — which only decides the rock's check_ok bit; then prev_ob <- ob.  The roots' arrays are never
+ *   written.  The per-rock entries live in pol->workspace, one slot per (rock, tree), copy on first touch; the touched set starts
+ *   empty at every simulation: the first CHECK of rock j in simulation s + 1 reads the ROOT's entry, not what simulation s left.
+ * Step 3, rollout mode.  The list is _generate_preferred over the private inputs at the simulated state (what
+ *   pomdp_preferred_actions returns: ascending action order); where the heuristic's own list is empty, it is _generate_legal().
+ *   a = list[(x * len(list)) >> 32] with the same ROLLOUT word x as pomdp_tree_search, keyed at t_s + k0.
+ *   Steps 1, 2, 4, 5, 6 and the backup are unchanged; tree-mode selection (step 2) still scans the LEGAL list.
+ * Node priors (prior_n > 0).  Let P(h) be the list the creating simulation's next rollout pick would come from: the preferred
+ *   list at the post-step state with the post-append private inputs, the fallback to the legal list included.  Every action a of
+ *   P(h) starts with N(h,a) = prior_n and V(h,a) = prior_v, every other action with 0 and 0.0, and Nh = sum_a N(h,a) therefore
+ *   starts at prior_n * |P(h)|.  Node 0 gets its priors from simulation 0 at its start — from that simulation's start state (its
+ *   particle, with particles) and the root's inputs — when D >= 1; with D == 0 nothing is simulated, no priors are set and the
+ *   outputs are pomdp_tree_search's.  A node created by a simulation's last step (k0 == D) is left without priors: no simulation
+ *   ever selects there.  The backup's V += (Rt - V) / (double)N runs on top of the priors.  tree_visits, tree_q and the merge
+ *   include the priors, each tree's own: merged visits count them W times.  Nh indexes logn up to S + A * prior_n.
+ * pol->workspace: device, 16-byte aligned, at least pomdp_tree_search_preferred_workspace(env, params, R * W) = 32 * num_rocks
+ *   bytes per tree for RockSample and 0 otherwise (pass NULL); it need not be initialised, its contents afterwards are unspecified.
+ * Refused with POMDP_E_BADARG / POMDP_E_BADPARAMS before anything is enqueued: everything pomdp_tree_search refuses; pol or
+ *   pol->history NULL (or a history with a NULL array the env reads); history->max_size != -1; RockSample without belief,
+ *   without prev_ob, or (R > 0) without a workspace, with a misaligned or a short one; prior_n < 0 or > 65535; prior_v not
+ *   finite; W * (S + A * prior_n) > 2^31 - 1.
+ * Envs without a policy of their own (Tiger, BattleShip, Network): prior_n == 0 forwards to pomdp_tree_search — the same
+ *   result bit for bit, pol's pointers ignored; prior_n > 0 is POMDP_E_BADARG (a uniform prior over the legal list steers
+ *   nothing).  For RockSample the heuristic always applies, as for pomdp_rollout_preferred.
+ * Two launches: the search (one lane per tree) and pomdp_tree_search's merge. */
+typedef struct pomdp_tree_policy {
+    const pomdp_rock_belief *belief;   /* RockSample: the roots' side statistics; NULL for Tag */
+    const pomdp_history     *history;  /* the roots' history sums; max_size must be -1 */
+    const int32_t           *prev_ob;  /* RockSample: device int32 [R] */
+    void    *workspace;                /* device, 16-byte aligned, uninitialised */
+    uint64_t workspace_bytes;
+    int32_t  prior_n;                  /* 0 = no priors */
+    int32_t  reserved;
+    double   prior_v;
+} pomdp_tree_policy;
+size_t pomdp_tree_search_preferred_workspace(int env, const void *params, int64_t n_trees);
+int    pomdp_tree_search_preferred(const pomdp_tree_args *a, const pomdp_tree_policy *pol, uint64_t t0, void *stream);
+
 int         pomdp_abi_version(void);
 const char *pomdp_error_string(int code);
 /* introspection: the kernel (name<template arguments>, as a profiler shows it) that the calling thread's most recent

@@ -3,7 +3,10 @@
 configs[4]'s shape by default: RockSample(15,15), 2048 roots, search with 16 trees per root x 64 simulations of depth 64
 against plan(64, 1024), both 1024 simulations per root, from the true states and from 256 particles per root.  The roots
 are a few real steps into their episodes.  One JSON line (profiles/r24_tree_search_timing.json), with the search kernel's
-resources (tools/kernel_resources.py; compiled on the spot, no GPU work).  Run it under `timeout`."""
+resources (tools/kernel_resources.py; compiled on the spot, no GPU work).  Run it under `timeout`.
+--preferred: the preferred-policy arm instead (profiles/r25_tree_search_timing.json) — an env with use_heuristic=True whose
+roots are `--prep` heuristic-policy steps into their episodes; search(policy="preferred", history=) without priors and with
+(--prior-n, --prior-v), and the uniform search() on the same roots in the same run, from the true states and from particles."""
 import argparse
 import json
 import os
@@ -43,8 +46,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--no-resources", action="store_true")
+    ap.add_argument("--preferred", action="store_true")
+    ap.add_argument("--prior-n", type=int, default=3)
+    ap.add_argument("--prior-v", type=float, default=5.0)
     args = ap.parse_args()
     import gym_pomdp_amd as gpa
+    if args.preferred:
+        return preferred_arm(args, gpa)
     e = gpa.make("Rock-v0", board_size=args.board, num_rocks=args.rocks, batch_size=args.roots, auto_reset=False, seed=1)
     ob = e.reset()
     bel = e.particle_belief(args.particles)
@@ -82,6 +90,50 @@ def main():
         import kernel_resources as kr
         want = "tree_search_kernel<RockEnv<%d, false> >" % (1 if args.rocks <= 12 else 2)
         res["resources"] = [r for r in kr.collect(units=["tree_search.hip"]) if r["kernel"] in (want, "tree_merge_kernel")]
+    print(json.dumps(res))
+
+
+def preferred_arm(args, gpa):
+    e = gpa.make("Rock-v0", board_size=args.board, num_rocks=args.rocks, batch_size=args.roots, auto_reset=False, seed=1,
+                 use_heuristic=True)
+    ob = e.reset()
+    hist = gpa.History(e)
+    bel = e.particle_belief(args.particles)
+    bel.reset(ob)
+    for _ in range(args.prep):
+        a, ob, rew, done = e.heuristic_steps(hist, 1)
+        bel.update(a, ob)
+    res = dict(tool="gpu_tree_search_timing --preferred", env="RockSample(%d,%d)" % (args.board, args.rocks), roots=args.roots,
+               trees_per_root=args.trees, sims_per_tree=args.sims, depth=args.depth, ucb_c=args.ucb_c, particles=args.particles,
+               sims_per_root=args.trees * args.sims, prep_heuristic_steps=args.prep, prior_n=args.prior_n, prior_v=args.prior_v,
+               reps=args.reps, warmup=args.warmup, device=torch.cuda.get_device_name(0))
+    arms = (("uniform", {}), ("preferred", dict(policy="preferred", history=hist)),
+            ("preferred_priors", dict(policy="preferred", history=hist, prior_n=args.prior_n, prior_v=args.prior_v)))
+    for name, b in (("true", None), ("particles", bel)):
+        for what, kw in arms:
+            out = e.search(args.depth, args.sims, args.trees, args.ucb_c, belief=b, diagnostics=True, **kw)
+            fn = lambda: e.search(args.depth, args.sims, args.trees, args.ucb_c, belief=b, out=out, diagnostics=True, **kw)
+            for _ in range(args.warmup):
+                fn()
+            torch.cuda.synchronize()
+            med, lo, hi = timed(fn, args.reps)
+            key = "%s_%s" % (name, what)
+            res[key + "_ms"], res[key + "_min_ms"], res[key + "_max_ms"] = round(med, 4), round(lo, 4), round(hi, 4)
+            steps = int(out["sim_steps"].sum().item())
+            res[key + "_sim_steps"] = steps
+            res[key + "_tree_steps"] = int(out["sim_tree_steps"].sum().item())
+            res[key + "_steps_per_s"] = round(steps / (med * 1e-3), 1)
+            res[key + "_mean_nodes"] = round(float(out["n_nodes"].double().mean().item()), 2)
+            if "_policy_workspace" in out:
+                res["policy_workspace_bytes"] = int(out["_policy_workspace"].numel() * 8)
+            res["workspace_bytes"] = int(out["_workspace"].numel() * 8)
+        for what in ("preferred", "preferred_priors"):
+            res["%s_%s_over_uniform" % (name, what)] = round(res["%s_%s_ms" % (name, what)] / res["%s_uniform_ms" % name], 3)
+    if not args.no_resources:
+        import kernel_resources as kr
+        v = 1 if args.rocks <= 12 else 2
+        res["resources"] = [r for r in kr.collect(units=["tree_search_preferred.hip"]) if r["kernel"] == "tree_preferred_kernel<RockEnv<%d, false> >" % v] + \
+                           [r for r in kr.collect(units=["tree_search.hip"]) if r["kernel"] == "tree_search_kernel<RockEnv<%d, false> >" % v]
     print(json.dumps(res))
 
 
