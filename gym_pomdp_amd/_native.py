@@ -17,8 +17,8 @@ LIB_PATH = os.environ.get("GYM_POMDP_AMD_LIB") or INTREE_LIB_PATH
 # one object per translation unit (built in parallel), linked into one shared library
 UNITS = ["api.hip", "step_rock.hip", "step_other.hip", "fused_rock.hip", "fused_stochrock.hip", "fused_tag.hip",
          "fused_battleship.hip", "fused_misc.hip", "planner.hip", "episodes.hip",
-         "particles.hip", "planner_preferred.hip", "heuristic_collect.hip", "controller.hip", "tree_search.hip", "tree_search_preferred.hip"]
-HEADERS = ["kernels_common.hip.h", "planner_common.hip.h", "heuristic_impl.hip.h", "traj_out.hip.h", "step_impl.hip.h", "fused_impl.hip.h", "envs.hip.h", "envs_common.hip.h", "philox.hip.h", "tree_pool.hip.h",
+         "particles.hip", "planner_preferred.hip", "heuristic_collect.hip", "controller.hip", "tree_search.hip", "tree_search_preferred.hip", "tree_keep.hip"]
+HEADERS = ["kernels_common.hip.h", "planner_common.hip.h", "heuristic_impl.hip.h", "traj_out.hip.h", "step_impl.hip.h", "fused_impl.hip.h", "envs.hip.h", "envs_common.hip.h", "philox.hip.h", "tree_pool.hip.h", "tree_keep.hip.h",
            "envs/rock.hip.h", "envs/tag.hip.h", "envs/battleship.hip.h", "envs/tiger.hip.h", "envs/network.hip.h"]
 SOURCES = [os.path.join(_PKG, "csrc", f) for f in UNITS + HEADERS]
 HEADER = os.path.join(_REPO, "include", "pomdp_hip.h")
@@ -47,6 +47,7 @@ SYMBOLS = [
     "pomdp_rollout_preferred_workspace", "pomdp_rollout_preferred", "pomdp_plan_preferred",
     "pomdp_tree_search_workspace", "pomdp_tree_search",
     "pomdp_tree_search_preferred_workspace", "pomdp_tree_search_preferred",
+    "pomdp_tree_keep_workspace", "pomdp_tree_search_resume", "pomdp_tree_advance",
 ]
 
 
@@ -138,6 +139,11 @@ class PlanTreeArgs(C.Structure):    # pomdp_tree_args
 class PlanTreePolicy(C.Structure):  # pomdp_tree_policy
     _fields_ = [("belief", C.c_void_p), ("history", C.c_void_p), ("prev_ob", C.c_void_p), ("workspace", C.c_void_p),
                 ("workspace_bytes", C.c_uint64), ("prior_n", C.c_int32), ("reserved", C.c_int32), ("prior_v", C.c_double)]
+
+
+class PlanTreeKeep(C.Structure):    # pomdp_tree_keep
+    _fields_ = [("workspace", C.c_void_p), ("workspace_bytes", C.c_uint64), ("n_nodes", C.c_void_p), ("node_capacity", C.c_int64),
+                ("logn_len", C.c_int64)]
 
 
 class Returns(C.Structure):         # pomdp_returns
@@ -277,6 +283,12 @@ def lib():
     L.pomdp_tree_search_preferred_workspace.argtypes = [ci, vp, i64]
     L.pomdp_tree_search_preferred.restype = ci
     L.pomdp_tree_search_preferred.argtypes = [vp, vp, u64, vp]
+    L.pomdp_tree_keep_workspace.restype = C.c_size_t
+    L.pomdp_tree_keep_workspace.argtypes = [ci, vp, i64, i64, ci]
+    L.pomdp_tree_search_resume.restype = ci
+    L.pomdp_tree_search_resume.argtypes = [vp, vp, u64, vp]
+    L.pomdp_tree_advance.restype = ci
+    L.pomdp_tree_advance.argtypes = [ci, vp, i64, ci, ci, vp, vp, vp, vp, vp, vp]
     L.pomdp_particle_init.restype = ci
     L.pomdp_particle_init.argtypes = [ci, vp, vp, vp, vp, vp, i64, ci, u64, u32, u64, vp]
     L.pomdp_particle_update.restype = ci

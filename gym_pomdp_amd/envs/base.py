@@ -847,7 +847,7 @@ class BatchedEnv(compat.EnvBase):
         return res + (p,)
 
     def search(self, depth, sims_per_tree, trees_per_root, ucb_c, discount=None, belief=None, out=None, diagnostics=False,
-               policy="uniform", history=None, prior_n=0, prior_v=0.0):
+               policy="uniform", history=None, prior_n=0, prior_v=0.0, tree=None):
         """POMCP's tree search from the live state (pomdp_tree_search): for every lane `trees_per_root` independent UCB1 trees
         over action-observation histories, each grown by `sims_per_tree` simulations of at most `depth` steps — UCB1 with
         exploration constant `ucb_c` inside the tree, one new node per simulation, a uniform random rollout over
@@ -869,7 +869,13 @@ class BatchedEnv(compat.EnvBase):
         env or the History is written.  `prior_n` > 0 (at most 65535) with `prior_v`: a new node's preferred actions start with
         N = prior_n and V = prior_v ("smart tree"), and "tree_visits" / "visits" include those counts.  The envs whose
         preferred list is the legal list, and a RockSample env built without use_heuristic, run the uniform search; with
-        prior_n > 0 they raise ValueError: a uniform prior over the legal list steers nothing."""
+        prior_n > 0 they raise ValueError: a uniform prior over the legal list steers nothing.
+        `tree` (a SearchTree of this env, trees_per_root and depth: env.search_tree(...)): the uniform search resumed from the
+        nodes `tree` holds (pomdp_tree_search_resume) — empty trees at first, after tree.advance(action, ob) the subtrees under
+        the real step.  "tree_visits" / "visits" then include the kept visits, "n_nodes" are the trees' sizes afterwards (also
+        tree.n_nodes), and a tree that has filled its node_capacity keeps simulating without growing.  The preferred-policy
+        search does not resume yet: `tree` with policy="preferred" raises ValueError on RockSample with use_heuristic=True
+        and on Tag."""
         import math
         preferred = self._preferred_policy("search", policy, history, False, None)
         prior_n, prior_v = int(prior_n), float(prior_v)
@@ -883,6 +889,11 @@ class BatchedEnv(compat.EnvBase):
             raise ValueError("search: the belief belongs to another env shape (%r)" % (belief,))
         R, n_act = self._state.shape[1], self.action_space.n
         D, S, W = int(depth), int(sims_per_tree), int(trees_per_root)
+        if tree is not None:
+            if preferred:
+                raise ValueError("search: the preferred-policy search does not resume yet: tree= needs policy='uniform' on this env")
+            if not tree._belongs(self, W, D):
+                raise ValueError("search: the SearchTree belongs to another env shape, trees_per_root or depth")
         n = R * W
         lane0 = self.lane_offset * W
         if W < 1 or S < 1 or D < 0 or lane0 + n > 1 << 32:
@@ -908,6 +919,8 @@ class BatchedEnv(compat.EnvBase):
             out["sim_ret"] = torch.empty((S, n), dtype=torch.float64, device=self.device)
             out["sim_steps"] = torch.empty((S, n), dtype=torch.int32, device=self.device)
             out["sim_tree_steps"] = torch.empty((S, n), dtype=torch.int32, device=self.device)
+        if tree is not None:
+            return self._search_resume(tree, out, belief, diagnostics, R, W, S, D, c, discount, lane0, n_act)
         nbytes = int(self._lib.pomdp_tree_search_workspace(kind, self._params_ref, n, S, D))
         if nbytes == 0 and n > 0:
             raise ValueError("search: pomdp_tree_search_workspace refuses %d trees x %d simulations x depth %d" % (n, S, D))
@@ -953,8 +966,36 @@ class BatchedEnv(compat.EnvBase):
             _native.check(rc, "pomdp_tree_search")
         return out
 
+    def _search_resume(self, tree, out, belief, diagnostics, R, W, S, D, c, discount, lane0, n_act):
+        """search(tree=...) after its checks: pomdp_tree_search_resume into the buffers of `out`"""
+        logn, keep = tree._begin_search(S)
+        diag = lambda k: out[k].data_ptr() if diagnostics else None
+        args = _native.PlanTreeArgs(
+            env=_native.ENV_KIND[self.env_name], depth=D, params=C.addressof(self._params), root_state=self._state.data_ptr(),
+            particles=None if belief is None else belief.particles.data_ptr(), n_roots=R,
+            n_particles=0 if belief is None else belief.n_particles, trees_per_root=W, sims_per_tree=S,
+            discount=float(self._discount if discount is None else discount), ucb_c=c, logn=logn.data_ptr(),
+            workspace=None, workspace_bytes=0, tree_visits=out["tree_visits"].data_ptr(),
+            tree_q=out["tree_q"].data_ptr(), n_nodes=out["n_nodes"].data_ptr(), sim_ret=diag("sim_ret"),
+            sim_steps=diag("sim_steps"), sim_tree_steps=diag("sim_tree_steps"),
+            out=_native.PlanOut(q=out["q"].data_ptr(), visits=out["visits"].data_ptr(), best=out["best"].data_ptr(),
+                                value=out["value"].data_ptr(), stride=n_act, reserved=0),
+            seed=self._seed, lane0=lane0, reserved=0)
+        t0 = self._t
+        self._t += S * D
+        with torch.cuda.device(self.device):
+            rc = self._lib.pomdp_tree_search_resume(C.byref(args), C.byref(keep), t0, self._stream())
+            _native.check(rc, "pomdp_tree_search_resume")
+        return out
+
+    def search_tree(self, trees_per_root, node_capacity=None, depth=64, sims_per_tree=None):
+        """A SearchTree for search(tree=...) / search_step(tree=...) of this env: `trees_per_root` trees per lane, each a pool of
+        `node_capacity` nodes (None with `sims_per_tree=`: 2 * sims_per_tree + 1), for searches of this `depth`."""
+        from ..search_tree import SearchTree
+        return SearchTree(self, trees_per_root, node_capacity, depth, sims_per_tree)
+
     def search_step(self, depth, sims_per_tree, trees_per_root, ucb_c, discount=None, belief=None, out=None, diagnostics=False,
-                    policy="uniform", history=None, prior_n=0, prior_v=0.0):
+                    policy="uniform", history=None, prior_n=0, prior_v=0.0, tree=None):
         """One REAL step of every lane, searched: search() from the live state (or from `belief`'s particles), then step(best)
         and, with `belief`, belief.update(best, ob, reward, done) — what plan_step() is to plan().  Returns (ob, reward, done,
         info, search dict).  A lane whose search took no step (best == -1) is handed -1, which step() counts as an invalid
@@ -962,7 +1003,13 @@ class BatchedEnv(compat.EnvBase):
         `policy="preferred"` with `history=` (and `prior_n`, `prior_v`): search() under the env's preferred-action policy, then
         the agent's knowledge follows the real step exactly as in plan_step(): step() updates RockSample's side statistics, the
         transition (history.prev_ob, best, reward, ob, done) is appended to `history` and history.prev_ob becomes ob — next to
-        belief.update(...) when `belief` is given.  Needs auto_reset=False for the same reason."""
+        belief.update(...) when `belief` is given.  Needs auto_reset=False for the same reason.
+        `tree` (search()): the search resumes from `tree`, and after the real step tree.advance(best, ob, drop=done) keeps the
+        subtrees under it: the trees of ended lanes and of lanes with best == -1 end up empty.  Needs auto_reset=False: a
+        restarted lane's tree would be the old episode's."""
+        if tree is not None and self._auto_reset:
+            raise ValueError("search_step(tree=...) needs auto_reset=False: restart ended lanes with env.reset(where=done); "
+                             "their trees are already empty")
         if belief is not None and self._auto_reset:
             raise ValueError("search_step(belief=...) needs auto_reset=False: restart ended lanes with env.reset(where=done) and "
                              "belief.reset(ob, where=done)")
@@ -970,12 +1017,14 @@ class BatchedEnv(compat.EnvBase):
             raise ValueError("search_step(policy='preferred') needs auto_reset=False: restart ended lanes with "
                              "env.reset(where=done) and history.clear(where=done)")
         p = self.search(depth, sims_per_tree, trees_per_root, ucb_c, discount, belief=belief, out=out, diagnostics=diagnostics,
-                        policy=policy, history=history, prior_n=prior_n, prior_v=prior_v)
+                        policy=policy, history=history, prior_n=prior_n, prior_v=prior_v, tree=tree)
         a = p["best"]
         if self.batch_size == 1:
             a = int(a.item())
             assert a >= 0, "search_step: no simulation took a step"
         res = self.step(a)
+        if tree is not None:
+            tree.advance(p["best"], res[0], drop=res[2])
         if history is not None:
             from ..history import Transition
             history.append(Transition(history.prev_ob, a, res[1], res[0], res[2]), auto_reset=False)

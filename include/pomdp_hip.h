@@ -916,6 +916,63 @@ typedef struct pomdp_tree_policy {
 size_t pomdp_tree_search_preferred_workspace(int env, const void *params, int64_t n_trees);
 int    pomdp_tree_search_preferred(const pomdp_tree_args *a, const pomdp_tree_policy *pol, uint64_t t0, void *stream);
 
+/* ---- trees kept between searches (added to ABI 15: new entry points only, nothing existing changes) -----------------------
+ * POMCP's other half: after the real step (a, o) the child h.a.o of the root becomes the new root, and its statistics and
+ * everything below it carry into the next search.  pomdp_tree_search_resume searches from the trees a workspace holds;
+ * pomdp_tree_advance copies, per tree, the subtree under the real step into a second workspace.  The uniform search only.
+ * A kept tree is a pool of C = node_capacity nodes in k->workspace (device, 16-byte aligned, at least
+ *   pomdp_tree_keep_workspace(env, params, R * W, C, D) bytes; 0 = the shape is refused: C < 1, C * A > 2^31 - 1, D < 0, more
+ *   than any device holds) and a count k->n_nodes[i] (device int32 [R * W]); tree i = r * W + w as for pomdp_tree_search.  The
+ *   workspace needs no initialisation where the count says "empty".  Per node the pool holds pomdp_tree_search's N(h,a),
+ *   V(h,a), the child links and Nh = the node's visits (sum_a N(h,a) for every node a search made).
+ *
+ * pomdp_tree_search_resume is pomdp_tree_search with these differences, stated against that contract's numbered steps; every
+ * float64 operation is one of its own (no new one is added: a kept statistic is a stored value).
+ * Start.  Tree i starts from the k->n_nodes[i] nodes k->workspace holds.  k->n_nodes[i] < 1 means empty: node 0 is cleared
+ *   (N = V = 0, no child, Nh = 0) and the count becomes 1.  A count above C is read as C.  a->workspace and a->workspace_bytes
+ *   are ignored.
+ * Pool.  The pool has C nodes; S may exceed C - 1.
+ * Step 6 on a full pool.  If child (h, a, o) does not exist and the tree holds C nodes, no node is created and nothing in the
+ *   tree is written; the mode becomes rollout all the same (k0 = k, the rollout words keyed at t_s + k0 from the next step),
+ *   and the path pushed so far and the backup are as always.
+ * Step 2.  logn has k->logn_len entries (logn[n] = log(n), entry 0 never read) and Nh is clamped to logn_len - 1.  A node's Nh
+ *   grows by at most S per search: a table of (searches since the trees were empty) * S + 1 entries is never clamped.
+ * Path.  The in-tree steps of a simulation number at most min(D, C): each is taken at an existing node, the child of the one
+ *   before.
+ * Outputs.  tree_visits and tree_q are node 0's N and V — kept visits included, so visits[r] may exceed W * S; a->n_nodes and
+ *   k->n_nodes both receive the trees' sizes afterwards.  The merge is pomdp_tree_search's, unchanged.
+ * Anchor.  From empty trees with C = S + 1 and logn_len = S + 1 every output equals pomdp_tree_search's bit for bit.
+ * Refused before anything is enqueued (POMDP_E_BADARG / POMDP_E_BADPARAMS): everything pomdp_tree_search refuses except its
+ *   workspace and (S + 1) * A rules; k or k->n_nodes NULL; C < 1; C * A > 2^31 - 1; logn_len < 2; W * (logn_len - 1) > 2^31 - 1
+ *   (merged visits are int32); with R > 0 a NULL, misaligned or short k->workspace.  n_roots == 0 returns 0.
+ * Two launches: the search (one lane per tree) and pomdp_tree_search's merge.
+ *
+ * pomdp_tree_advance, for tree i of root r (one lane per tree, no atomics; src is only read):
+ *   dst->n_nodes[i] = 0 (an empty tree; its pool in dst->workspace is left as it was) if drop != NULL and drop[r] != 0, or
+ *   action[r] is outside [0, A), or src->n_nodes[i] < 1, or (node 0, action[r]) has no child with observation ob[r].
+ *   Otherwise the subtree rooted at that child is copied into dst, renumbered breadth-first (a Cheney copy): the kept child is
+ *   node 0, with observation 0 and no sibling; a node's actions are scanned in ascending order, and the children of one (h, a)
+ *   keep their chain order.  Every copied node keeps its N, V, child links (renumbered) and Nh.  dst->n_nodes[i] = the count.
+ *   The destination is its own queue: a pending node's source index waits in the node's spare fourth word.
+ *   The copy ends and stays inside both pools for arbitrary workspace contents: every index read from memory is clamped
+ *   before use, every chain walk is guarded, and the copy stops at C nodes.
+ *   action, ob: device int32 [R]; drop: device uint8 [R] or NULL.  depth is the D both workspaces were sized with.
+ * Refused before anything is enqueued: NULL params / src / dst / action / ob, an unknown env or bad params, R < 0, W < 1, D < 0,
+ *   R * W > 2^32, either descriptor as for pomdp_tree_search_resume (logn_len is not read), src == dst, src->node_capacity !=
+ *   dst->node_capacity, workspaces or count arrays that overlap.  n_roots == 0 returns 0.  One launch. */
+typedef struct pomdp_tree_keep {
+    void    *workspace;       /* device, 16-byte aligned: the kept trees */
+    uint64_t workspace_bytes; /* >= pomdp_tree_keep_workspace(...) */
+    int32_t *n_nodes;         /* device int32 [R * W], in/out: nodes held by tree i; < 1 = empty tree */
+    int64_t  node_capacity;   /* C >= 1: nodes per tree */
+    int64_t  logn_len;        /* entries of a->logn; Nh is clamped to logn_len - 1 */
+} pomdp_tree_keep;
+size_t pomdp_tree_keep_workspace(int env, const void *params, int64_t n_trees, int64_t node_capacity, int depth);
+int pomdp_tree_search_resume(const pomdp_tree_args *a, const pomdp_tree_keep *k, uint64_t t0, void *stream);
+int pomdp_tree_advance(int env, const void *params, int64_t n_roots, int trees_per_root, int depth,
+                       const pomdp_tree_keep *src, const pomdp_tree_keep *dst,
+                       const int32_t *action, const int32_t *ob, const uint8_t *drop, void *stream);
+
 int         pomdp_abi_version(void);
 const char *pomdp_error_string(int code);
 /* introspection: the kernel (name<template arguments>, as a profiler shows it) that the calling thread's most recent

@@ -6,7 +6,12 @@ are a few real steps into their episodes.  One JSON line (profiles/r24_tree_sear
 resources (tools/kernel_resources.py; compiled on the spot, no GPU work).  Run it under `timeout`.
 --preferred: the preferred-policy arm instead (profiles/r25_tree_search_timing.json) — an env with use_heuristic=True whose
 roots are `--prep` heuristic-policy steps into their episodes; search(policy="preferred", history=) without priors and with
-(--prior-n, --prior-v), and the uniform search() on the same roots in the same run, from the true states and from particles."""
+(--prior-n, --prior-v), and the uniform search() on the same roots in the same run, from the true states and from particles.
+--keep: the kept-tree arm instead (profiles/r26_tree_keep_timing.json), from the true states and from particles: search() — the
+yardstick, its kernel untouched —, search(tree=) from empty trees, search(tree=) on the `--keep-step`-th consecutive
+search_step(tree=) of the same roots, and tree.advance() alone, with the nodes kept and held there; then `--episodes` Tag
+episodes of at most `--episode-steps` steps played by search_step() with and without tree= at the same budget: the mean
+discounted return of each (recorded, not judged)."""
 import argparse
 import json
 import os
@@ -49,10 +54,17 @@ def main():
     ap.add_argument("--preferred", action="store_true")
     ap.add_argument("--prior-n", type=int, default=3)
     ap.add_argument("--prior-v", type=float, default=5.0)
+    ap.add_argument("--keep", action="store_true")
+    ap.add_argument("--capacity", type=int, default=None, help="nodes per kept tree (default 2 * sims + 1)")
+    ap.add_argument("--keep-step", type=int, default=10)
+    ap.add_argument("--episodes", type=int, default=2048)
+    ap.add_argument("--episode-steps", type=int, default=90)
     args = ap.parse_args()
     import gym_pomdp_amd as gpa
     if args.preferred:
         return preferred_arm(args, gpa)
+    if args.keep:
+        return keep_arm(args, gpa)
     e = gpa.make("Rock-v0", board_size=args.board, num_rocks=args.rocks, batch_size=args.roots, auto_reset=False, seed=1)
     ob = e.reset()
     bel = e.particle_belief(args.particles)
@@ -133,6 +145,116 @@ def preferred_arm(args, gpa):
         import kernel_resources as kr
         v = 1 if args.rocks <= 12 else 2
         res["resources"] = [r for r in kr.collect(units=["tree_search_preferred.hip"]) if r["kernel"] == "tree_preferred_kernel<RockEnv<%d, false> >" % v] + \
+                           [r for r in kr.collect(units=["tree_search.hip"]) if r["kernel"] == "tree_search_kernel<RockEnv<%d, false> >" % v]
+    print(json.dumps(res))
+
+
+def stats(ms):
+    ms = sorted(ms)
+    return round(ms[len(ms) // 2], 4), round(ms[0], 4), round(ms[-1], 4)
+
+
+def keep_arm(args, gpa):
+    D, S, W, c = args.depth, args.sims, args.trees, args.ucb_c
+    Cn = 2 * S + 1 if args.capacity is None else args.capacity
+    e = gpa.make("Rock-v0", board_size=args.board, num_rocks=args.rocks, batch_size=args.roots, auto_reset=False, seed=1)
+    ob = e.reset()
+    bel = e.particle_belief(args.particles)
+    bel.reset(ob)
+    for _ in range(args.prep):
+        a = e.synthetic_actions()
+        ob, rew, done, _ = e.step(a)
+        bel.update(a, ob)
+    res = dict(tool="gpu_tree_search_timing --keep", env="RockSample(%d,%d)" % (args.board, args.rocks), roots=args.roots,
+               trees_per_root=W, sims_per_tree=S, depth=D, ucb_c=c, particles=args.particles, node_capacity=Cn,
+               keep_step=args.keep_step, reps=args.reps, warmup=args.warmup, device=torch.cuda.get_device_name(0))
+    state0, t0, done0 = e.state.clone(), e.call_counter, e.done.clone()
+    parts0, tb0 = bel.particles.clone(), bel.call_counter
+    tree = e.search_tree(W, Cn, D)
+    res["keep_workspace_bytes"] = 2 * tree._bytes
+    ev = lambda: torch.cuda.Event(enable_timing=True)
+
+    def restore():
+        e.set_state(state0)
+        e._done.copy_(done0)
+        e.call_counter = t0
+        bel.set_particles(parts0)
+        bel.call_counter = tb0
+        tree.clear()
+
+    for name, b in (("true", None), ("particles", bel)):
+        restore()
+        s_out = e.search(D, S, W, c, belief=b)
+        e.call_counter = t0
+        k_out = e.search(D, S, W, c, belief=b, tree=tree)
+        res["%s_empty_equals_search" % name] = bool(all(torch.equal(s_out[k], k_out[k]) for k in ("q", "visits", "best", "value")))
+        # arm 1: search(), the parent's kernel; arm 2: the resumed search from empty trees (cleared outside the timed span)
+        for what, fn, before in (("search", lambda: e.search(D, S, W, c, belief=b, out=s_out), lambda: None),
+                                 ("resume_empty", lambda: e.search(D, S, W, c, belief=b, out=k_out, tree=tree), tree.clear)):
+            ms = []
+            for i in range(args.warmup + args.reps):
+                e.call_counter = t0
+                before()
+                x, y = ev(), ev()
+                x.record()
+                fn()
+                y.record()
+                y.synchronize()
+                if i >= args.warmup:
+                    ms.append(x.elapsed_time(y))
+            res["%s_%s_ms" % (name, what)], res["%s_%s_min_ms" % (name, what)], res["%s_%s_max_ms" % (name, what)] = stats(ms)
+        lo, hi, med = res["%s_search_min_ms" % name], res["%s_search_max_ms" % name], res["%s_resume_empty_ms" % name]
+        res["%s_resume_empty_over_search" % name] = round(med / res["%s_search_ms" % name], 4)
+        res["%s_resume_empty_inside_search_spread" % name] = bool(lo <= med <= hi)
+        # arm 3: the search of the keep_step-th consecutive search_step(tree=); arm 4: its advance alone
+        ms_s, ms_a, kept, held, live = [], [], [], [], []
+        for i in range(args.warmup + args.reps):
+            restore()
+            for _ in range(args.keep_step - 1):
+                e.search_step(D, S, W, c, belief=b, out=k_out, tree=tree)
+            kept.append(float(tree.n_nodes.double().mean().item()))
+            live.append(float((tree.n_nodes > 0).double().mean().item()))
+            x, y, z, w = ev(), ev(), ev(), ev()
+            x.record()
+            p = e.search(D, S, W, c, belief=b, out=k_out, tree=tree)
+            y.record()
+            o2, r2, d2, _ = e.step(p["best"])
+            z.record()
+            tree.advance(p["best"], o2, drop=d2)
+            w.record()
+            w.synchronize()
+            held.append(float(p["n_nodes"].double().mean().item()))
+            if i >= args.warmup:
+                ms_s.append(x.elapsed_time(y))
+                ms_a.append(z.elapsed_time(w))
+        res["%s_resume_kept_ms" % name], res["%s_resume_kept_min_ms" % name], res["%s_resume_kept_max_ms" % name] = stats(ms_s)
+        res["%s_advance_ms" % name], res["%s_advance_min_ms" % name], res["%s_advance_max_ms" % name] = stats(ms_a)
+        res["%s_mean_kept_nodes" % name] = round(kept[-1], 3)                 # per tree, before the timed search (empty trees count 0)
+        res["%s_trees_with_kept_nodes" % name] = round(live[-1], 4)
+        res["%s_mean_nodes_after" % name] = round(held[-1], 3)
+        res["%s_lanes_done" % name] = round(float(e.done.double().mean().item()), 4)
+    # whether reuse changes the decisions: Tag episodes from the true states, with and without tree=, the same seeds
+    for name, use in (("tag_without_tree", False), ("tag_with_tree", True)):
+        t = gpa.make("Tag-v0", batch_size=args.episodes, auto_reset=False, seed=1)
+        t.reset()
+        tr = t.search_tree(W, Cn, D) if use else None
+        ret = torch.zeros(args.episodes, dtype=torch.float64, device=t.device)
+        disc, out = 1.0, None
+        for _ in range(args.episode_steps):
+            if use and W * (tr.searches + 1) * S > 0x7FFFFFFF:
+                tr.clear()
+            kw = dict(tree=tr) if use else {}
+            o2, r2, d2, _, out = t.search_step(D, S, W, 10.0, out=out, **kw)
+            ret += disc * r2.double()                                         # a frozen lane's reward is 0
+            disc *= t._discount
+        res[name + "_mean_return"] = round(float(ret.mean().item()), 4)
+        res[name + "_return_stderr"] = round(float(ret.std().item()) / args.episodes ** .5, 4)
+        res[name + "_episodes_ended"] = round(float(t.done.double().mean().item()), 4)
+    res.update(tag_episodes=args.episodes, tag_episode_steps=args.episode_steps, tag_ucb_c=10.0)
+    if not args.no_resources:
+        import kernel_resources as kr
+        v = 1 if args.rocks <= 12 else 2
+        res["resources"] = [r for r in kr.collect(units=["tree_keep.hip"]) if r["kernel"] in ("tree_resume_kernel<RockEnv<%d, false> >" % v, "tree_advance_kernel")] + \
                            [r for r in kr.collect(units=["tree_search.hip"]) if r["kernel"] == "tree_search_kernel<RockEnv<%d, false> >" % v]
     print(json.dumps(res))
 
