@@ -17,7 +17,8 @@ LIB_PATH = os.environ.get("GYM_POMDP_AMD_LIB") or INTREE_LIB_PATH
 # one object per translation unit (built in parallel), linked into one shared library
 UNITS = ["api.hip", "step_rock.hip", "step_other.hip", "fused_rock.hip", "fused_stochrock.hip", "fused_tag.hip",
          "fused_battleship.hip", "fused_misc.hip", "planner.hip", "episodes.hip",
-         "particles.hip", "planner_preferred.hip", "heuristic_collect.hip", "controller.hip", "tree_search.hip", "tree_search_preferred.hip", "tree_keep.hip"]
+         "particles.hip", "planner_preferred.hip", "heuristic_collect.hip", "controller.hip", "tree_search.hip", "tree_search_preferred.hip", "tree_keep.hip",
+         "tree_keep_preferred.hip"]
 HEADERS = ["kernels_common.hip.h", "planner_common.hip.h", "heuristic_impl.hip.h", "traj_out.hip.h", "step_impl.hip.h", "fused_impl.hip.h", "envs.hip.h", "envs_common.hip.h", "philox.hip.h", "tree_pool.hip.h", "tree_keep.hip.h",
            "envs/rock.hip.h", "envs/tag.hip.h", "envs/battleship.hip.h", "envs/tiger.hip.h", "envs/network.hip.h"]
 SOURCES = [os.path.join(_PKG, "csrc", f) for f in UNITS + HEADERS]
@@ -48,6 +49,7 @@ SYMBOLS = [
     "pomdp_tree_search_workspace", "pomdp_tree_search",
     "pomdp_tree_search_preferred_workspace", "pomdp_tree_search_preferred",
     "pomdp_tree_keep_workspace", "pomdp_tree_search_resume", "pomdp_tree_advance",
+    "pomdp_tree_search_preferred_resume",
 ]
 
 
@@ -287,6 +289,8 @@ def lib():
     L.pomdp_tree_keep_workspace.argtypes = [ci, vp, i64, i64, ci]
     L.pomdp_tree_search_resume.restype = ci
     L.pomdp_tree_search_resume.argtypes = [vp, vp, u64, vp]
+    L.pomdp_tree_search_preferred_resume.restype = ci
+    L.pomdp_tree_search_preferred_resume.argtypes = [vp, vp, vp, u64, vp]
     L.pomdp_tree_advance.restype = ci
     L.pomdp_tree_advance.argtypes = [ci, vp, i64, ci, ci, vp, vp, vp, vp, vp, vp]
     L.pomdp_particle_init.restype = ci

@@ -1,8 +1,9 @@
 // tree_keep.hip.h — what a tree kept between searches adds to the node pool of tree_pool.hip.h (include/pomdp_hip.h:
 // pomdp_tree_search_resume, pomdp_tree_advance): the layout of a pool of C nodes, a child lookup / insert that reports a full
 // pool, and the copy of the subtree under one child of the root into another pool.  __host__ __device__ and free of device
-// builtins like tree_pool.hip.h, so that the same text runs in the kernels (tree_keep.hip) and in a stand-alone host program
-// (tools/tree_keep_hostcheck.cpp, built with the host sanitizers).
+// builtins like tree_pool.hip.h, so that the same text runs in the kernels (tree_keep.hip, tree_keep_preferred.hip) and in
+// stand-alone host programs (tools/tree_keep_hostcheck.cpp, tools/tree_keep_preferred_hostcheck.cpp, built with the host
+// sanitizers).  At its end: what the preferred-policy search needs on such a pool, priors for a node that may have them.
 //
 // Layout: tree_pool.hip.h's three arrays with a node capacity C that no longer follows from the simulation count,
 //   edge [C][A], node [C], path [min(D, C)].
@@ -108,6 +109,60 @@ static POMDP_TREE_HD int32_t tree_keep_copy(const TreeView &src, int32_t n_src, 
         }
     }
     return count;
+}
+
+// What a kept tree adds where the search sets node priors (pomdp_tree_search_preferred_resume).  A kept node may or may not
+// have received its priors: the one a simulation's last step created has none, and after the advance a later search stands
+// on it.  Stored Nh == 0 says "neither primed nor visited" — priming sets Nh = prior_n * |P(h)| >= 1 and every backup adds
+// one — so no flag word is needed and the spare word stays the copy's.
+// tree_node_priors for a node h of a pool that holds n_nodes nodes, applied only while the node's stored Nh is 0: the ONE
+// read of the node word decides, and its Nh comes back for the selection that follows (-> the node's Nh afterwards).  With
+// Nh != 0, with prior_n < 1 or with h outside [0, n_nodes) nothing is written; otherwise the stores are tree_node_priors's:
+// the node's A edges and its visit count, nothing else.
+template <class In>
+static POMDP_TREE_HD int32_t tree_node_priors_once(const TreeView &t, int32_t h, int32_t n_nodes, In in, int32_t prior_n, double prior_v)
+{
+    if (h < 0 || h > t.d.S || h >= n_nodes) return 0;
+    const int32_t nh = t.node[h].visits;
+    const int32_t pn = prior_n < 0 ? 0 : (prior_n > 65535 ? 65535 : prior_n);
+    if (nh != 0 || pn == 0) return nh;
+    int32_t listed = 0;
+    for (int32_t a = 0; a < t.d.A; ++a) {
+        const bool on = in(a);
+        TreeEdge e; e.v = on ? prior_v : 0.0; e.n = on ? pn : 0; e.child = 0;
+        t.edge[(int64_t)h * t.d.A + a] = e;
+        listed += (int32_t)on;
+    }
+    t.node[h].visits = pn * listed;
+    return pn * listed;
+}
+
+// tree_select_clamped with the node's Nh handed in (what tree_node_priors_once returned) instead of read again: the same
+// scan, the same four float64 operations per visited action, none fused.
+template <class Pick>
+static POMDP_TREE_HD int32_t tree_select_nh(const TreeView &t, int32_t h, int32_t nh, int count, Pick pick, double ucb_c, const double *logn,
+                                            int32_t nh_max)
+{
+#pragma clang fp contract(off)
+    const int32_t hc = tree_clamp_node(t, h);
+    nh = nh < 0 ? 0 : (nh > nh_max ? nh_max : nh);
+    const double ln = logn[nh];
+    int32_t fresh = -1, best = -1;
+    double bu = 0.0;
+    for (int i = 0; i < count; ++i) {
+        const int32_t a = pick(i);
+        const TreeEdge e = t.edge[tree_edge_index(t, hc, a)];
+        if (e.n == 0) {
+            if (fresh < 0) fresh = a;
+        } else {
+            const double ratio = ln / (double)e.n;
+            const double root = __builtin_sqrt(ratio);
+            const double bonus = ucb_c * root;
+            const double u = e.v + bonus;
+            if (best < 0 || u > bu) { best = a; bu = u; }
+        }
+    }
+    return fresh >= 0 ? fresh : best;
 }
 
 } // namespace pomdp

@@ -873,9 +873,12 @@ class BatchedEnv(compat.EnvBase):
         `tree` (a SearchTree of this env, trees_per_root and depth: env.search_tree(...)): the uniform search resumed from the
         nodes `tree` holds (pomdp_tree_search_resume) — empty trees at first, after tree.advance(action, ob) the subtrees under
         the real step.  "tree_visits" / "visits" then include the kept visits, "n_nodes" are the trees' sizes afterwards (also
-        tree.n_nodes), and a tree that has filled its node_capacity keeps simulating without growing.  The preferred-policy
-        search does not resume yet: `tree` with policy="preferred" raises ValueError on RockSample with use_heuristic=True
-        and on Tag."""
+        tree.n_nodes), and a tree that has filled its node_capacity keeps simulating without growing.  A tree is bound to the
+        policy it is grown under: on RockSample with use_heuristic=True and on Tag, policy="preferred" resumes only a tree
+        built with search_tree(..., policy="preferred", prior_n=, prior_v=) (pomdp_tree_search_preferred_resume) and takes its
+        priors from the tree — prior_n / prior_v that differ from the tree's raise ValueError, the defaults mean "the
+        tree's" —, a kept node is primed once, by the first simulation that stands on it while its Nh is 0; a default tree
+        under policy="preferred", and a preferred tree under policy="uniform", raise ValueError."""
         import math
         preferred = self._preferred_policy("search", policy, history, False, None)
         prior_n, prior_v = int(prior_n), float(prior_v)
@@ -890,8 +893,17 @@ class BatchedEnv(compat.EnvBase):
         R, n_act = self._state.shape[1], self.action_space.n
         D, S, W = int(depth), int(sims_per_tree), int(trees_per_root)
         if tree is not None:
+            if preferred and tree.policy != "preferred":
+                raise ValueError("search: the preferred-policy search does not resume a tree grown without priors: tree= needs "
+                                 "policy='uniform' on this env, or build the tree with search_tree(..., policy='preferred')")
+            if not preferred and tree.policy == "preferred":
+                raise ValueError("search: a SearchTree built with policy='preferred' is resumed by search(policy='preferred', "
+                                 "history=...) only: its nodes carry priors the uniform search does not lay")
             if preferred:
-                raise ValueError("search: the preferred-policy search does not resume yet: tree= needs policy='uniform' on this env")
+                if (prior_n, prior_v) != (0, 0.0) and (prior_n, prior_v) != (tree.prior_n, tree.prior_v):
+                    raise ValueError("search: prior_n=%r, prior_v=%r differ from the SearchTree's (%r, %r): with tree= the priors "
+                                     "are the tree's" % (prior_n, prior_v, tree.prior_n, tree.prior_v))
+                prior_n, prior_v = tree.prior_n, tree.prior_v
             if not tree._belongs(self, W, D):
                 raise ValueError("search: the SearchTree belongs to another env shape, trees_per_root or depth")
         n = R * W
@@ -920,7 +932,8 @@ class BatchedEnv(compat.EnvBase):
             out["sim_steps"] = torch.empty((S, n), dtype=torch.int32, device=self.device)
             out["sim_tree_steps"] = torch.empty((S, n), dtype=torch.int32, device=self.device)
         if tree is not None:
-            return self._search_resume(tree, out, belief, diagnostics, R, W, S, D, c, discount, lane0, n_act)
+            return self._search_resume(tree, out, belief, diagnostics, R, W, S, D, c, discount, lane0, n_act,
+                                       history if preferred else None)
         nbytes = int(self._lib.pomdp_tree_search_workspace(kind, self._params_ref, n, S, D))
         if nbytes == 0 and n > 0:
             raise ValueError("search: pomdp_tree_search_workspace refuses %d trees x %d simulations x depth %d" % (n, S, D))
@@ -966,8 +979,9 @@ class BatchedEnv(compat.EnvBase):
             _native.check(rc, "pomdp_tree_search")
         return out
 
-    def _search_resume(self, tree, out, belief, diagnostics, R, W, S, D, c, discount, lane0, n_act):
-        """search(tree=...) after its checks: pomdp_tree_search_resume into the buffers of `out`"""
+    def _search_resume(self, tree, out, belief, diagnostics, R, W, S, D, c, discount, lane0, n_act, history=None):
+        """search(tree=...) after its checks: pomdp_tree_search_resume — with `history` (a preferred tree)
+        pomdp_tree_search_preferred_resume under the tree's priors — into the buffers of `out`"""
         logn, keep = tree._begin_search(S)
         diag = lambda k: out[k].data_ptr() if diagnostics else None
         args = _native.PlanTreeArgs(
@@ -983,16 +997,35 @@ class BatchedEnv(compat.EnvBase):
             seed=self._seed, lane0=lane0, reserved=0)
         t0 = self._t
         self._t += S * D
+        if history is not None:
+            rock = self.env_name == "rock"
+            pbytes = int(self._lib.pomdp_tree_search_preferred_workspace(args.env, self._params_ref, R * W))
+            pws = tree._policy_workspace                     # scratch, uninitialised between calls: held by the tree
+            if pws is None or pws.numel() * 8 != pbytes:
+                pws = tree._policy_workspace = torch.empty((pbytes // 16, 2), dtype=torch.float64, device=self.device)
+            pol = _native.PlanTreePolicy(
+                belief=C.addressof(self._tracker.ptrs) if rock else None, history=C.addressof(history._ptrs),
+                prev_ob=history.prev_ob.data_ptr() if rock else None, workspace=pws.data_ptr() if pbytes else None,
+                workspace_bytes=pbytes, prior_n=tree.prior_n, reserved=0, prior_v=tree.prior_v)
+            with torch.cuda.device(self.device):
+                rc = self._lib.pomdp_tree_search_preferred_resume(C.byref(args), C.byref(pol), C.byref(keep), t0, self._stream())
+                _native.check(rc, "pomdp_tree_search_preferred_resume")
+            return out
         with torch.cuda.device(self.device):
             rc = self._lib.pomdp_tree_search_resume(C.byref(args), C.byref(keep), t0, self._stream())
             _native.check(rc, "pomdp_tree_search_resume")
         return out
 
-    def search_tree(self, trees_per_root, node_capacity=None, depth=64, sims_per_tree=None):
+    def search_tree(self, trees_per_root, node_capacity=None, depth=64, sims_per_tree=None, policy="uniform", prior_n=0,
+                    prior_v=0.0):
         """A SearchTree for search(tree=...) / search_step(tree=...) of this env: `trees_per_root` trees per lane, each a pool of
-        `node_capacity` nodes (None with `sims_per_tree=`: 2 * sims_per_tree + 1), for searches of this `depth`."""
+        `node_capacity` nodes (None with `sims_per_tree=`: 2 * sims_per_tree + 1), for searches of this `depth`.
+        `policy` binds the tree to the search that grows it: "uniform" (the default), or "preferred" with the node priors
+        `prior_n` / `prior_v` for search(policy="preferred", history=..., tree=tree) on RockSample with use_heuristic=True and
+        on Tag.  On the envs whose preferred search is the uniform one, "preferred" with prior_n == 0 gives a uniform tree and
+        prior_n > 0 raises ValueError, as search() does."""
         from ..search_tree import SearchTree
-        return SearchTree(self, trees_per_root, node_capacity, depth, sims_per_tree)
+        return SearchTree(self, trees_per_root, node_capacity, depth, sims_per_tree, policy, prior_n, prior_v)
 
     def search_step(self, depth, sims_per_tree, trees_per_root, ucb_c, discount=None, belief=None, out=None, diagnostics=False,
                     policy="uniform", history=None, prior_n=0, prior_v=0.0, tree=None):

@@ -1,5 +1,6 @@
 """The search trees of BatchedEnv.search(tree=...) kept between real steps (include/pomdp_hip.h: pomdp_tree_search_resume,
-pomdp_tree_advance): the device-resident node pools, and the step that makes the real step's child the new root."""
+pomdp_tree_search_preferred_resume, pomdp_tree_advance): the device-resident node pools, and the step that makes the real
+step's child the new root."""
 import ctypes as C
 import math
 
@@ -22,10 +23,29 @@ class SearchTree(object):
     Merged visit counts are int32: once W * searches * S would pass 2^31 - 1 the next search raises ValueError — clear() the
     tree (it restarts the count).
 
+    A tree is bound to the policy it is grown under.  policy="uniform" (the default) is resumed by the uniform search.
+    policy="preferred" on an env with a preferred-action policy of its own (RockSample with use_heuristic=True, Tag) is
+    resumed by search(policy="preferred", history=...) and carries the node priors prior_n / prior_v: a tree grown without
+    priors must not be continued by a search that assumes them, nor the other way round.  Priors are laid once per node, so
+    Nh can reach searches * S + A * prior_n, and the table and the int32 bound count that term.  On the other envs the
+    preferred search IS the uniform one: policy="preferred" with prior_n == 0 gives a uniform tree, prior_n > 0 raises.
+
     n_nodes: int32 [R * W], the nodes each tree holds (< 1: empty).  to_host(i): tree i decoded, for tests and debugging."""
 
-    def __init__(self, env, trees_per_root, node_capacity=None, depth=64, sims_per_tree=None):
+    def __init__(self, env, trees_per_root, node_capacity=None, depth=64, sims_per_tree=None, policy="uniform", prior_n=0,
+                 prior_v=0.0):
         W, D = int(trees_per_root), int(depth)
+        if policy not in ("uniform", "preferred"):
+            raise ValueError("search_tree: policy must be 'uniform' or 'preferred', got %r" % (policy,))
+        prior_n, prior_v = int(prior_n), float(prior_v)
+        if prior_n < 0 or prior_n > 65535 or not math.isfinite(prior_v):
+            raise ValueError("search_tree: needs 0 <= prior_n <= 65535 and a finite prior_v, got %r, %r" % (prior_n, prior_v))
+        own_policy = env.env_name == "tag" or (env.env_name == "rock" and env._use_heuristic)
+        if prior_n > 0 and not (policy == "preferred" and own_policy):
+            raise ValueError("search_tree: prior_n > 0 needs policy='preferred' on an env with a preferred-action policy of its "
+                             "own (RockSample with use_heuristic=True, Tag): a uniform prior over the legal list steers nothing")
+        self.policy = "preferred" if (policy == "preferred" and own_policy) else "uniform"
+        self.prior_n, self.prior_v = (prior_n, prior_v) if self.policy == "preferred" else (0, 0.0)
         if node_capacity is None:
             if sims_per_tree is None:
                 raise ValueError("search_tree: give node_capacity, or sims_per_tree= for the default 2 * sims_per_tree + 1")
@@ -50,6 +70,7 @@ class SearchTree(object):
         self._cur = 0
         self.searches = 0
         self._logn = None
+        self._policy_workspace = None                        # RockSample's scratch of the preferred search, held for reuse
 
     @property
     def n_nodes(self):
@@ -67,10 +88,10 @@ class SearchTree(object):
 
     def _begin_search(self, S):
         """-> (the log table, the pomdp_tree_keep of the live trees) for one more search of S simulations per tree"""
-        need = (self.searches + 1) * int(S)                  # the largest Nh the search can reach
+        need = (self.searches + 1) * int(S) + self.n_actions * self.prior_n   # the largest Nh the search can reach
         if self.trees_per_root * need > 0x7FFFFFFF:
-            raise ValueError("search: trees_per_root * searches * sims_per_tree would pass 2^31 - 1 (merged visit counts are "
-                             "int32) after %d searches: clear() the SearchTree" % self.searches)
+            raise ValueError("search: trees_per_root * (searches * sims_per_tree + n_actions * prior_n) would pass 2^31 - 1 "
+                             "(merged visit counts are int32) after %d searches: clear() the SearchTree" % self.searches)
         if self._logn is None or self._logn.numel() < need + 1:
             n_log = min(max(need + 1, 2 * (0 if self._logn is None else self._logn.numel())), 0x7FFFFFFF // self.trees_per_root + 1)
             table = np.empty(n_log, np.float64)

@@ -919,7 +919,8 @@ int    pomdp_tree_search_preferred(const pomdp_tree_args *a, const pomdp_tree_po
 /* ---- trees kept between searches (added to ABI 15: new entry points only, nothing existing changes) -----------------------
  * POMCP's other half: after the real step (a, o) the child h.a.o of the root becomes the new root, and its statistics and
  * everything below it carry into the next search.  pomdp_tree_search_resume searches from the trees a workspace holds;
- * pomdp_tree_advance copies, per tree, the subtree under the real step into a second workspace.  The uniform search only.
+ * pomdp_tree_advance copies, per tree, the subtree under the real step into a second workspace.  pomdp_tree_search_resume is
+ * the uniform search; pomdp_tree_search_preferred_resume (further below) is the preferred-policy search on the same pools.
  * A kept tree is a pool of C = node_capacity nodes in k->workspace (device, 16-byte aligned, at least
  *   pomdp_tree_keep_workspace(env, params, R * W, C, D) bytes; 0 = the shape is refused: C < 1, C * A > 2^31 - 1, D < 0, more
  *   than any device holds) and a count k->n_nodes[i] (device int32 [R * W]); tree i = r * W + w as for pomdp_tree_search.  The
@@ -972,6 +973,45 @@ int pomdp_tree_search_resume(const pomdp_tree_args *a, const pomdp_tree_keep *k,
 int pomdp_tree_advance(int env, const void *params, int64_t n_roots, int trees_per_root, int depth,
                        const pomdp_tree_keep *src, const pomdp_tree_keep *dst,
                        const int32_t *action, const int32_t *ob, const uint8_t *drop, void *stream);
+
+/* ---- the preferred-policy search resumed from kept trees (added to ABI 15: one new entry point, nothing existing changes) ---
+ * pomdp_tree_search_preferred_resume is pomdp_tree_search_preferred with pomdp_tree_search_resume's differences applied, word
+ * for word as stated there with k: Start (tree i starts from the k->n_nodes[i] nodes k->workspace holds; < 1 = empty: node 0 is
+ * cleared and the count becomes 1; a->workspace is ignored), Pool (C nodes; S may exceed C - 1), Step 6 on a full pool (no node,
+ * nothing written, rollout mode from k0 = k all the same), Step 2 (logn has k->logn_len entries, Nh is clamped to logn_len - 1),
+ * Path (at most min(D, C) in-tree steps) and Outputs (tree_visits / tree_q are node 0's N and V, kept visits and priors
+ * included; a->n_nodes and k->n_nodes both receive the sizes afterwards).  pomdp_tree_advance is used between searches as it
+ * is.  No float64 operation is added: a prior and a kept statistic are stored values.  On top of the two contracts comes one rule.
+ * When a node receives priors (prior_n > 0).  A node is UNPRIMED while its stored Nh == 0.  Take an active lane — not done, with
+ *   a non-empty list — that is about to choose an action at a node h that exists in its pool: in tree mode before the
+ *   selection, or at the first rollout step after it created h, before the pick.  If h is unprimed, h first receives priors from
+ *   THIS step's P(h): the preferred list at the lane's current state and private inputs, the fallback to the legal list
+ *   included, exactly as pomdp_tree_search_preferred lays them (N = prior_n, V = prior_v on P(h), 0 and 0.0 elsewhere, no
+ *   child, Nh = sum_a N(h,a) = prior_n * |P(h)|, an action the list names twice counted once).  Consequences:
+ *   - An empty tree's node 0 is primed by the first simulation that takes a step — simulation 0 for RockSample and Tag, whose
+ *     lists are never empty — from that simulation's start state (its particle, with particles) and the root's inputs.
+ *   - A kept node 0 keeps the N, V and Nh it has and is not primed again.
+ *   - A node created by a simulation's last step (k0 == D) stays unprimed in that search, as in pomdp_tree_search_preferred.
+ *     After pomdp_tree_advance it sits one level higher; the first later simulation that stands on it primes it then, from
+ *     that simulation's state and private inputs.  The search from empty trees never meets this case.
+ *   - On a full pool no node exists, so nothing is primed.
+ *   - Nh > 0 means "primed or visited": P(h) is non-empty, so priming sets Nh = prior_n * |P(h)| >= 1, and every backup
+ *     increments Nh.  No flag word is needed; the node's spare word stays pomdp_tree_advance's.
+ *   A node's Nh can reach (searches since the trees were empty) * S + A * prior_n: priors are laid once per node.
+ * Private policy inputs are read from the roots at the start of every simulation, exactly as in pomdp_tree_search_preferred;
+ *   after a real step the caller's arrays reflect it.  The kept nodes' priors are the stored values their creating (or
+ *   priming) simulation laid; they are not recomputed.
+ * Anchor.  From empty trees with C = S + 1 and logn_len = S + 1 + A * prior_n every output equals
+ *   pomdp_tree_search_preferred's bit for bit, for every D.  With D == 0 nothing is primed.
+ * Refused before anything is enqueued (POMDP_E_BADARG / POMDP_E_BADPARAMS): everything pomdp_tree_search_preferred refuses
+ *   except its tree workspace and (S + 1) * A rules (and its W * (S + A * prior_n) rule, which the two below replace);
+ *   everything pomdp_tree_search_resume refuses about k; logn_len - 1 < A * prior_n + 1; W * (logn_len - 1) > 2^31 - 1.
+ *   n_roots == 0 returns 0.
+ * Envs without a policy of their own (Tiger, BattleShip, Network): prior_n == 0 forwards to pomdp_tree_search_resume — the
+ *   same result bit for bit, pol's pointers ignored; prior_n > 0 is POMDP_E_BADARG.
+ * Two launches: the search (one lane per tree) and pomdp_tree_search's merge. */
+int pomdp_tree_search_preferred_resume(const pomdp_tree_args *a, const pomdp_tree_policy *pol, const pomdp_tree_keep *k, uint64_t t0,
+                                       void *stream);
 
 int         pomdp_abi_version(void);
 const char *pomdp_error_string(int code);

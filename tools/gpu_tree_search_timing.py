@@ -11,7 +11,12 @@ roots are `--prep` heuristic-policy steps into their episodes; search(policy="pr
 yardstick, its kernel untouched —, search(tree=) from empty trees, search(tree=) on the `--keep-step`-th consecutive
 search_step(tree=) of the same roots, and tree.advance() alone, with the nodes kept and held there; then `--episodes` Tag
 episodes of at most `--episode-steps` steps played by search_step() with and without tree= at the same budget: the mean
-discounted return of each (recorded, not judged)."""
+discounted return of each (recorded, not judged).
+--keep --preferred: the kept-tree arm of the preferred-policy search (profiles/r27_tree_keep_preferred_timing.json) on the
+--preferred arm's roots, `--capacity` nodes per tree (default 2 * sims + 1), without priors and with (--prior-n, --prior-v), from
+the true states and from particles: search(policy="preferred") — the yardstick, its kernel untouched —, search(tree=) from
+empty preferred trees, the search of the `--keep-step`-th consecutive search_step(tree=) with the nodes kept there and the
+share of in-tree steps, and tree.advance() alone; then the Tag episodes as above under policy="preferred" with the priors."""
 import argparse
 import json
 import os
@@ -61,6 +66,8 @@ def main():
     ap.add_argument("--episode-steps", type=int, default=90)
     args = ap.parse_args()
     import gym_pomdp_amd as gpa
+    if args.keep and args.preferred:
+        return keep_preferred_arm(args, gpa)
     if args.preferred:
         return preferred_arm(args, gpa)
     if args.keep:
@@ -256,6 +263,119 @@ def keep_arm(args, gpa):
         v = 1 if args.rocks <= 12 else 2
         res["resources"] = [r for r in kr.collect(units=["tree_keep.hip"]) if r["kernel"] in ("tree_resume_kernel<RockEnv<%d, false> >" % v, "tree_advance_kernel")] + \
                            [r for r in kr.collect(units=["tree_search.hip"]) if r["kernel"] == "tree_search_kernel<RockEnv<%d, false> >" % v]
+    print(json.dumps(res))
+
+
+def keep_preferred_arm(args, gpa):
+    D, S, W, c = args.depth, args.sims, args.trees, args.ucb_c
+    Cn = 2 * S + 1 if args.capacity is None else args.capacity
+    res = dict(tool="gpu_tree_search_timing --keep --preferred", env="RockSample(%d,%d)" % (args.board, args.rocks), roots=args.roots,
+               trees_per_root=W, sims_per_tree=S, depth=D, ucb_c=c, particles=args.particles, node_capacity=Cn,
+               prep_heuristic_steps=args.prep, keep_step=args.keep_step, prior_v=args.prior_v, reps=args.reps, warmup=args.warmup,
+               device=torch.cuda.get_device_name(0))
+    ev = lambda: torch.cuda.Event(enable_timing=True)
+
+    def roots():
+        """the --preferred arm's roots, built anew: search_step() moves the env, its History and its side statistics"""
+        e = gpa.make("Rock-v0", board_size=args.board, num_rocks=args.rocks, batch_size=args.roots, auto_reset=False, seed=1,
+                     use_heuristic=True)
+        ob = e.reset()
+        hist = gpa.History(e)
+        bel = e.particle_belief(args.particles)
+        bel.reset(ob)
+        for _ in range(args.prep):
+            a, ob, rew, done = e.heuristic_steps(hist, 1)
+            bel.update(a, ob)
+        return e, hist, bel
+
+    for pn in (0, args.prior_n):
+        pkw = dict(policy="preferred", prior_n=pn, prior_v=args.prior_v if pn else 0.0)
+        for src in ("true", "particles"):
+            name = "%s_n%d" % (src, pn)
+            e, hist, bel = roots()
+            b = bel if src == "particles" else None
+            t0 = e.call_counter
+            tree = e.search_tree(W, Cn, D, **pkw)
+            res["keep_workspace_bytes"] = 2 * tree._bytes
+            s_out = e.search(D, S, W, c, belief=b, history=hist, **pkw)
+            e.call_counter = t0
+            k_out = e.search(D, S, W, c, belief=b, history=hist, policy="preferred", tree=tree)
+            res[name + "_empty_equals_search"] = bool(all(torch.equal(s_out[k], k_out[k]) for k in ("q", "visits", "best", "value")))
+            # arm 1: search(policy="preferred"), the parent's kernel; arm 2: resumed from empty trees (cleared outside the timed span)
+            for what, fn, before in (("search", lambda: e.search(D, S, W, c, belief=b, out=s_out, history=hist, **pkw), lambda: None),
+                                     ("resume_empty", lambda: e.search(D, S, W, c, belief=b, out=k_out, history=hist, policy="preferred",
+                                                                       tree=tree), tree.clear)):
+                ms = []
+                for i in range(args.warmup + args.reps):
+                    e.call_counter = t0
+                    before()
+                    x, y = ev(), ev()
+                    x.record()
+                    fn()
+                    y.record()
+                    y.synchronize()
+                    if i >= args.warmup:
+                        ms.append(x.elapsed_time(y))
+                res[name + "_%s_ms" % what], res[name + "_%s_min_ms" % what], res[name + "_%s_max_ms" % what] = stats(ms)
+            lo, hi, med = res[name + "_search_min_ms"], res[name + "_search_max_ms"], res[name + "_resume_empty_ms"]
+            res[name + "_resume_empty_over_search"] = round(med / res[name + "_search_ms"], 4)
+            res[name + "_resume_empty_inside_search_spread"] = bool(lo <= med <= hi)
+            # arm 3: the search of the keep_step-th consecutive search_step(tree=); arm 4: its advance alone
+            ms_s, ms_a = [], []
+            for i in range(args.warmup + args.reps):
+                e, hist, bel = roots()
+                b = bel if src == "particles" else None
+                tree = e.search_tree(W, Cn, D, **pkw)
+                out = None
+                for _ in range(args.keep_step - 1):                          # diagnostics on: `out` holds every buffer the timed search writes
+                    out = e.search_step(D, S, W, c, belief=b, out=out, history=hist, policy="preferred", tree=tree, diagnostics=True)[4]
+                kept = tree.n_nodes.clone()
+                x, y, z, w = ev(), ev(), ev(), ev()
+                x.record()
+                p = e.search(D, S, W, c, belief=b, out=out, history=hist, policy="preferred", tree=tree, diagnostics=True)
+                y.record()
+                o2, r2, d2, _ = e.step(p["best"])
+                z.record()
+                tree.advance(p["best"], o2, drop=d2)
+                w.record()
+                w.synchronize()
+                if i >= args.warmup:
+                    ms_s.append(x.elapsed_time(y))
+                    ms_a.append(z.elapsed_time(w))
+            res[name + "_resume_kept_ms"], res[name + "_resume_kept_min_ms"], res[name + "_resume_kept_max_ms"] = stats(ms_s)
+            res[name + "_advance_ms"], res[name + "_advance_min_ms"], res[name + "_advance_max_ms"] = stats(ms_a)
+            res[name + "_resume_kept_over_search"] = round(res[name + "_resume_kept_ms"] / res[name + "_search_ms"], 4)
+            res[name + "_mean_kept_nodes"] = round(float(kept.double().mean().item()), 3)     # per tree, before the timed search
+            res[name + "_max_kept_nodes"] = int(kept.max().item())
+            res[name + "_trees_with_kept_nodes"] = round(float((kept > 0).double().mean().item()), 4)
+            res[name + "_mean_nodes_after"] = round(float(p["n_nodes"].double().mean().item()), 3)
+            res[name + "_tree_step_share"] = round(float(p["sim_tree_steps"].sum().item()) / max(float(p["sim_steps"].sum().item()), 1.0), 4)
+            res[name + "_lanes_done"] = round(float(e.done.double().mean().item()), 4)
+    # whether reuse changes the decisions: Tag episodes from the true states under the preferred policy with priors
+    for name, use in (("tag_without_tree", False), ("tag_with_tree", True)):
+        t = gpa.make("Tag-v0", batch_size=args.episodes, auto_reset=False, seed=1)
+        t.reset()
+        th = gpa.History(t)
+        tr = t.search_tree(W, Cn, D, policy="preferred", prior_n=args.prior_n, prior_v=args.prior_v) if use else None
+        ret = torch.zeros(args.episodes, dtype=torch.float64, device=t.device)
+        disc, out = 1.0, None
+        for _ in range(args.episode_steps):
+            if use and W * ((tr.searches + 1) * S + 5 * args.prior_n) > 0x7FFFFFFF:
+                tr.clear()
+            kw = dict(tree=tr) if use else dict(prior_n=args.prior_n, prior_v=args.prior_v)
+            o2, r2, d2, _, out = t.search_step(D, S, W, 10.0, out=out, policy="preferred", history=th, **kw)
+            ret += disc * r2.double()                                         # a frozen lane's reward is 0
+            disc *= t._discount
+        res[name + "_mean_return"] = round(float(ret.mean().item()), 4)
+        res[name + "_return_stderr"] = round(float(ret.std().item()) / args.episodes ** .5, 4)
+        res[name + "_episodes_ended"] = round(float(t.done.double().mean().item()), 4)
+    res.update(tag_episodes=args.episodes, tag_episode_steps=args.episode_steps, tag_ucb_c=10.0, tag_prior_n=args.prior_n)
+    if not args.no_resources:
+        import kernel_resources as kr
+        v = 1 if args.rocks <= 12 else 2
+        res["resources"] = [r for r in kr.collect(units=["tree_keep_preferred.hip"]) if r["kernel"] == "tree_resume_preferred_kernel<RockEnv<%d, false> >" % v] + \
+                           [r for r in kr.collect(units=["tree_search_preferred.hip"]) if r["kernel"] == "tree_preferred_kernel<RockEnv<%d, false> >" % v] + \
+                           [r for r in kr.collect(units=["tree_keep.hip"]) if r["kernel"] == "tree_advance_kernel"]
     print(json.dumps(res))
 
 
