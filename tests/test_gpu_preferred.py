@@ -121,13 +121,14 @@ def columns_of(e, b):
     return e._state if b is None else b if torch.is_tensor(b) else b.particles
 
 
-def constructed(env, kw, R, prep, P=1, lane_offset=0, root_seed=ROOT_SEED):
+def constructed(env, kw, R, prep, P=1, lane_offset=0, root_seed=ROOT_SEED, **extra):
     """prepared() with the statistics overwritten by rr.construct_roots, on the GPU and as the restatement takes them
     -> (oracle env, env, History, ParticleBelief | None); for a P that ParticleBelief does not build, in its place the tensor
-    of the first P of every root's four particles, int32 [words, R * P], which only the C ABI takes"""
+    of the first P of every root's four particles, int32 [words, R * P], which only the C ABI takes; `extra` goes to make()
+    (seed=...)"""
     from oracle import oracle_lib as ol
     o = ol.OracleEnv(env, **kw)
-    e, hist, b = prepared(env, kw, R, prep, P if P % 4 == 0 or P == 1 else 4, lane_offset)
+    e, hist, b = prepared(env, kw, R, prep, P if P % 4 == 0 or P == 1 else 4, lane_offset, **extra)
     if b is not None and b.n_particles != P:
         b = b.particles.reshape(-1, R, 4)[:, :, :P].reshape(-1, R * P).contiguous()
     belief, history, pob = roots_of(e, hist)

@@ -39,11 +39,14 @@ REACHED = {"tiger": {"kept8", "frozen"}, "rock7-8": {"frozen"}, "rock15-15": set
            "battleship5x5": {"kept8", "ended"}, "network": {"nomatch"}}
 
 
-def play(env, kw, row, check_trees=True):
-    """`steps` real steps through search_step(tree=), each compared with the restatement -> what the restatement reached"""
+def play(env, kw, row, check_trees=True, seed=SEED, t0=None, c=None, discount=None):
+    """`steps` real steps through search_step(tree=), each compared with the restatement -> what the restatement reached.
+    seed, t0 (the call counter of the first search), c (ucb_c) and discount default to SEED, the counter after the warm-up,
+    UCB[env] and the env's own"""
     R, W, lane_offset, S, D, Cn, P, steps = row
-    c = UCB[env]
-    o, e, b = setup(env, kw, R, lane_offset, P)
+    c = UCB[env] if c is None else c
+    o, e, b = setup(env, kw, R, lane_offset, P, t0=t0, seed=seed)
+    gamma = e._discount if discount is None else discount
     tree = e.search_tree(W, Cn, D)
     assert (np_(tree.n_nodes) == 0).all() and tree.to_host(0) == {}
     trees, logn, n = None, ts.log_table(steps * S), R * W
@@ -52,9 +55,9 @@ def play(env, kw, row, check_trees=True):
     for step in range(steps):
         was_done = np_(e.done).astype(bool).reshape(R).copy()
         t0 = e.call_counter
-        want = tk.search(o, u32(e.state).copy(), R, W, S, D, e._discount, c, SEED, lane_offset * W, t0, trees=trees, C=Cn, logn=logn,
+        want = tk.search(o, u32(e.state).copy(), R, W, S, D, gamma, c, seed, lane_offset * W, t0, trees=trees, C=Cn, logn=logn,
                          particles=None if b is None else u32(b.particles).copy(), P=P)
-        ob, rew, done, info, got = e.search_step(D, S, W, c, belief=b, out=out, diagnostics=True, tree=tree)
+        ob, rew, done, info, got = e.search_step(D, S, W, c, discount=discount, belief=b, out=out, diagnostics=True, tree=tree)
         out = got
         assert e.call_counter == t0 + S * D + 1 and tree.searches == step + 1
         same(got, want, (env, kw, row, step))
@@ -72,6 +75,7 @@ def play(env, kw, row, check_trees=True):
                 assert tk.same_canon(tree.to_host(i), tk.canon(trees[i])), (env, row, step, i)
         live = ~dn & (a >= 0)
         seen["kept"] = max(seen["kept"], int(sizes.max()))
+        seen.setdefault("kept_per_step", []).append(int(sizes.max()))
         seen["nomatch"] += int((sizes.reshape(R, W)[live] == 0).sum())
         seen["ended"] += int((dn & ~was_done).sum())
         seen["frozen"] += int(was_done.sum())

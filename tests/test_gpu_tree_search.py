@@ -16,7 +16,8 @@ import tree_search_restatement as ts  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-ENV_IDS = {"rock": "Rock-v0", "tag": "Tag-v0", "battleship": "Battleship-v0", "tiger": "Tiger-v0", "network": "Network-v0"}
+ENV_IDS = {"rock": "Rock-v0", "stochrock": "StochasticRock-v0", "tag": "Tag-v0", "battleship": "Battleship-v0", "tiger": "Tiger-v0",
+           "network": "Network-v0"}
 ENVS = [("tiger", {}), ("rock", {}), ("rock", dict(board_size=15, num_rocks=15)), ("tag", {}), ("battleship", {}), ("network", {})]
 ENV_NAMES = ["tiger", "rock7-8", "rock15-15", "tag", "battleship5x5", "network"]
 # (R, W, lane_offset, S, D, ucb_c, P): every env runs every row
@@ -61,12 +62,12 @@ def same(got, want, what):
                                  % (what, k, len(bad), bad[0], g[tuple(bad[0])], want[k][tuple(bad[0])]))
 
 
-def setup(env, kw, R, lane_offset=0, P=0, warm=2, t0=None):
+def setup(env, kw, R, lane_offset=0, P=0, warm=2, t0=None, seed=SEED):
     """an env `warm` synthetic steps into its episodes (so that roots differ in more than their hidden state), its belief
     when P > 0, and the oracle of the same configuration"""
     from oracle import oracle_lib as ol
     o = ol.OracleEnv(env, **kw)
-    e = make(env, kw, R, lane_offset=lane_offset)
+    e = make(env, kw, R, lane_offset=lane_offset, seed=seed)
     ob = e.reset()
     b = None
     if P:
@@ -83,8 +84,8 @@ def setup(env, kw, R, lane_offset=0, P=0, warm=2, t0=None):
     return o, e, b
 
 
-def restate(o, e, b, W, S, D, c, discount=None):
-    return ts.search(o, u32(e.state), e.batch_size, W, S, D, e._discount if discount is None else discount, c, SEED,
+def restate(o, e, b, W, S, D, c, discount=None, seed=SEED):
+    return ts.search(o, u32(e.state), e.batch_size, W, S, D, e._discount if discount is None else discount, c, seed,
                      e.lane_offset * W, e.call_counter, particles=None if b is None else u32(b.particles),
                      P=0 if b is None else b.n_particles)
 

@@ -21,6 +21,7 @@ from oracle.philox_ref import stream_words
 
 M64 = ts.M64
 MUTATIONS = ("no_refill", "no_tree_update", "no_fallback_priors", "root_priors_every_sim", "nh_without_priors")
+KEY_MUTATIONS = ("k0_at_root",)          # tree_search_restatement's, for test_tree_edges_host.py: the ROLLOUT counter t_s, not t_s + k0
 COUNTERS = rr.COUNTERS + ("recheck_across_sims", "prior_from_fallback")
 
 
@@ -71,7 +72,7 @@ def search(o, states, belief, history, prev_ob, R, W, S, D, discount, ucb_c, see
     without priors) and "prior_sizes": per tree, |P(h)| of every node that got priors.
     states: uint32 [words, R] (P == 0: the true states) or [words, R * P]; belief / history / prev_ob: the roots' policy inputs
     as preferred_rollout_restatement takes them."""
-    assert mutate is None or mutate in MUTATIONS
+    assert mutate is None or mutate in MUTATIONS + KEY_MUTATIONS
     n, A = R * W, o.n_actions
     rock = rr.is_rock(o)
     K = A - 5 if rock else 0
@@ -184,8 +185,8 @@ def search(o, states, belief, history, prev_ob, R, W, S, D, discount, ucb_c, see
                             h[i] = kids[key] = trees[i].new_node()
                             k0[i] = k + 1
                             unprimed[i] = prior_n > 0
-                            words[i] = stream_words(seed, lane0 + i, (tsim + int(k0[i])) & M64, ts.STREAM_ROLLOUT,
-                                                    max(D - int(k0[i]), 1))
+                            tk = tsim if mutate == "k0_at_root" else (tsim + int(k0[i])) & M64
+                            words[i] = stream_words(seed, lane0 + i, tk, ts.STREAM_ROLLOUT, max(D - int(k0[i]), 1))
                 else:
                     acc[i] = acc[i] + disc[i] * r
                     disc[i] = disc[i] * np.float64(discount)
