@@ -21,6 +21,7 @@ from .history import EpisodeStats, History, Returns, Transition  # noqa: F401
 from .envs import BattleShipEnv, NetworkEnv, RockEnv, StochasticRockEnv, TagEnv, TigerEnv  # noqa: F401
 from .particles import ParticleBelief  # noqa: F401
 from .controller import Controller  # noqa: F401
+from .stoch_controller import StochasticController  # noqa: F401
 from .search_tree import SearchTree  # noqa: F401
 
 __version__ = "0.1.0"

@@ -17,9 +17,9 @@ LIB_PATH = os.environ.get("GYM_POMDP_AMD_LIB") or INTREE_LIB_PATH
 # one object per translation unit (built in parallel), linked into one shared library
 UNITS = ["api.hip", "step_rock.hip", "step_other.hip", "fused_rock.hip", "fused_stochrock.hip", "fused_tag.hip",
          "fused_battleship.hip", "fused_misc.hip", "planner.hip", "episodes.hip",
-         "particles.hip", "planner_preferred.hip", "heuristic_collect.hip", "controller.hip", "tree_search.hip", "tree_search_preferred.hip", "tree_keep.hip",
+         "particles.hip", "planner_preferred.hip", "heuristic_collect.hip", "controller.hip", "controller_stoch.hip", "tree_search.hip", "tree_search_preferred.hip", "tree_keep.hip",
          "tree_keep_preferred.hip"]
-HEADERS = ["kernels_common.hip.h", "planner_common.hip.h", "heuristic_impl.hip.h", "traj_out.hip.h", "step_impl.hip.h", "fused_impl.hip.h", "envs.hip.h", "envs_common.hip.h", "philox.hip.h", "tree_pool.hip.h", "tree_keep.hip.h",
+HEADERS = ["kernels_common.hip.h", "planner_common.hip.h", "heuristic_impl.hip.h", "traj_out.hip.h", "step_impl.hip.h", "fused_impl.hip.h", "envs.hip.h", "envs_common.hip.h", "philox.hip.h", "tree_pool.hip.h", "tree_keep.hip.h", "controller_common.hip.h",
            "envs/rock.hip.h", "envs/tag.hip.h", "envs/battleship.hip.h", "envs/tiger.hip.h", "envs/network.hip.h"]
 SOURCES = [os.path.join(_PKG, "csrc", f) for f in UNITS + HEADERS]
 HEADER = os.path.join(_REPO, "include", "pomdp_hip.h")
@@ -43,7 +43,7 @@ SYMBOLS = [
     "pomdp_rollout_synthetic", "pomdp_collect_synthetic", "pomdp_collect", "pomdp_collect_layout", "pomdp_collect_traj", "pomdp_packed_reward", "pomdp_decode_packed", "pomdp_collect_returns", "pomdp_collect_tape", "pomdp_collect_tape_layout", "pomdp_collect_tape_returns", "pomdp_fuse_max", "pomdp_fuse_steps", "pomdp_legal_actions", "pomdp_rollout", "pomdp_plan", "pomdp_plan_reduce", "pomdp_compute_prob",
     "pomdp_rock_belief_reset", "pomdp_rock_belief_refresh", "pomdp_rock_belief_update", "pomdp_rock_select_target", "pomdp_history_clear",
     "pomdp_history_append", "pomdp_preferred_actions", "pomdp_pick_actions", "pomdp_heuristic_steps", "pomdp_heuristic_collect",
-    "pomdp_reset_where", "pomdp_finish_episodes", "pomdp_controller_episodes",
+    "pomdp_reset_where", "pomdp_finish_episodes", "pomdp_controller_episodes", "pomdp_stoch_controller_episodes",
     "pomdp_particle_init", "pomdp_particle_update", "pomdp_plan_particles",
     "pomdp_rollout_preferred_workspace", "pomdp_rollout_preferred", "pomdp_plan_preferred",
     "pomdp_tree_search_workspace", "pomdp_tree_search",
@@ -122,6 +122,12 @@ class EpisodeArgs(C.Structure):     # pomdp_episode_args
 
 class Controller(C.Structure):      # pomdp_controller
     _fields_ = [("action", C.c_void_p), ("next", C.c_void_p), ("n_nodes", C.c_int32), ("n_obs", C.c_int32), ("node", C.c_void_p)]
+
+
+class StochController(C.Structure):      # pomdp_stoch_controller
+    _fields_ = [("action", C.c_void_p), ("action_thr", C.c_void_p), ("next", C.c_void_p), ("next_thr", C.c_void_p),
+                ("n_nodes", C.c_int32), ("n_obs", C.c_int32), ("n_act_cand", C.c_int32), ("n_next_cand", C.c_int32),
+                ("node", C.c_void_p)]
 
 
 class PlanOut(C.Structure):         # pomdp_plan_out
@@ -324,6 +330,8 @@ def lib():
     L.pomdp_finish_episodes.argtypes = [vp, u64, i64, vp]
     L.pomdp_controller_episodes.restype = ci
     L.pomdp_controller_episodes.argtypes = [vp, vp, u64, i64, vp]
+    L.pomdp_stoch_controller_episodes.restype = ci
+    L.pomdp_stoch_controller_episodes.argtypes = [vp, vp, u64, i64, vp]
     L.pomdp_philox_blocks.restype = ci
     L.pomdp_philox_blocks.argtypes = [vp, vp, i64, vp]
     _lib = L

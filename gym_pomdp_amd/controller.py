@@ -30,7 +30,70 @@ def _as_int32(a):
     return np.where((a < -(1 << 31)) | (a >= 1 << 31), -1, a).astype(np.int32)
 
 
-class Controller(object):
+class _LaneNodes(object):
+    """What every controller class keeps per lane: `node` (int32 [N] on the env's device, lane i's current node; in/out of
+    every run_controller call), the `start` nodes in their three forms, and reset_nodes().  A subclass sets env, device,
+    n_nodes, n_obs and validate, then calls _init_nodes(start)."""
+
+    def _init_nodes(self, start):
+        self.node = torch.zeros(self.env.batch_size, dtype=torch.int32, device=self.device)
+        self.start = start
+        if self._start_kind != "table":
+            self.reset_nodes()
+
+    # ---- start nodes ---------------------------------------------------------------------------------------------------------
+    @property
+    def start(self):
+        return self._start
+
+    @start.setter
+    def start(self, start):
+        N = self.node.shape[0]
+        if isinstance(start, (int, np.integer)):
+            s, kind = np.asarray(int(start), np.int64), "int"
+        else:
+            s = _int_array(start, "start")
+            kind = "lanes" if s.shape == (N,) else "table" if s.shape == (self.n_obs,) else None
+            if kind is None:
+                raise ValueError("%s: start must be an int, an int [%d] array (per lane) or an int [%d] table (per reset "
+                                 "observation), got shape %s" % (type(self).__name__, N, self.n_obs, s.shape))
+        if self.validate:
+            bad = _first_outside(s.reshape(-1), self.n_nodes)
+            if bad is not None:
+                raise ValueError("%s: start%s = %d is outside [0, %d)"
+                                 % (type(self).__name__, "" if kind == "int" else "[%d]" % bad[0], s.reshape(-1)[bad], self.n_nodes))
+        self._start_kind = kind
+        self._start = int(s) if kind == "int" else torch.as_tensor(_as_int32(s), device=self.device)
+
+    def reset_nodes(self, ob=None, where=None):
+        """Put lanes back on their start nodes: all of them, or those with where[i] != 0 (bool / integer [N]) — the companion
+        of env.reset(where=env.done).  env.done is the live flag buffer and that reset clears it, so reset the nodes first, or
+        keep the mask: `fin = env.done.clone(); ob = env.reset(where=fin); ctrl.reset_nodes(ob=ob, where=fin)`.  `ob` (int
+        [N], what that reset returned) is needed when `start` is a table per reset observation; the entries of lanes outside
+        `where` (-1 from a masked reset) are not used.  Plain torch, asynchronous.  Returns `node`."""
+        N = self.node.shape[0]
+        if self._start_kind == "int":
+            new = torch.full_like(self.node, self._start)
+        elif self._start_kind == "lanes":
+            new = self._start
+        else:
+            if ob is None:
+                raise ValueError("%s.reset_nodes: start is a table per reset observation — pass ob" % type(self).__name__)
+            o = ob.to(self.device) if isinstance(ob, torch.Tensor) else torch.as_tensor(np.asarray(ob), device=self.device)
+            if o.shape != (N,) or o.dtype.is_floating_point:
+                raise ValueError("%s.reset_nodes: ob must be an int [%d] array" % (type(self).__name__, N))
+            new = self._start[o.long().clamp(0, self.n_obs - 1)]
+        if where is None:
+            self.node.copy_(new)
+        else:
+            w = where.to(self.device) if isinstance(where, torch.Tensor) else torch.as_tensor(np.asarray(where), device=self.device)
+            if w.shape != (N,) or w.dtype.is_floating_point:
+                raise ValueError("%s.reset_nodes: where must be a bool / integer [%d] array" % (type(self).__name__, N))
+            self.node.copy_(torch.where(w != 0, new, self.node))
+        return self.node
+
+
+class Controller(_LaneNodes):
     """Controller(env, action, next, start=0, validate=True)
 
     action: integer array-like [K] — the action of node q.  next: integer array-like [K, env.observation_space.n] — the
@@ -70,61 +133,13 @@ class Controller(object):
         self.device = env.device
         self.action = torch.as_tensor(_as_int32(a), device=self.device)
         self.next = torch.as_tensor(_as_int32(nx), device=self.device).contiguous()
-        self.node = torch.zeros(env.batch_size, dtype=torch.int32, device=self.device)
-        self.start = start
-        if self._start_kind != "table":
-            self.reset_nodes()
+        self._init_nodes(start)
 
-    # ---- start nodes ---------------------------------------------------------------------------------------------------------
-    @property
-    def start(self):
-        return self._start
-
-    @start.setter
-    def start(self, start):
-        N = self.node.shape[0]
-        if isinstance(start, (int, np.integer)):
-            s, kind = np.asarray(int(start), np.int64), "int"
-        else:
-            s = _int_array(start, "start")
-            kind = "lanes" if s.shape == (N,) else "table" if s.shape == (self.n_obs,) else None
-            if kind is None:
-                raise ValueError("Controller: start must be an int, an int [%d] array (per lane) or an int [%d] table (per reset "
-                                 "observation), got shape %s" % (N, self.n_obs, s.shape))
-        if self.validate:
-            bad = _first_outside(s.reshape(-1), self.n_nodes)
-            if bad is not None:
-                raise ValueError("Controller: start%s = %d is outside [0, %d)"
-                                 % ("" if kind == "int" else "[%d]" % bad[0], s.reshape(-1)[bad], self.n_nodes))
-        self._start_kind = kind
-        self._start = int(s) if kind == "int" else torch.as_tensor(_as_int32(s), device=self.device)
-
-    def reset_nodes(self, ob=None, where=None):
-        """Put lanes back on their start nodes: all of them, or those with where[i] != 0 (bool / integer [N]) — the companion
-        of env.reset(where=env.done).  env.done is the live flag buffer and that reset clears it, so reset the nodes first, or
-        keep the mask: `fin = env.done.clone(); ob = env.reset(where=fin); ctrl.reset_nodes(ob=ob, where=fin)`.  `ob` (int
-        [N], what that reset returned) is needed when `start` is a table per reset observation; the entries of lanes outside
-        `where` (-1 from a masked reset) are not used.  Plain torch, asynchronous.  Returns `node`."""
-        N = self.node.shape[0]
-        if self._start_kind == "int":
-            new = torch.full_like(self.node, self._start)
-        elif self._start_kind == "lanes":
-            new = self._start
-        else:
-            if ob is None:
-                raise ValueError("Controller.reset_nodes: start is a table per reset observation — pass ob")
-            o = ob.to(self.device) if isinstance(ob, torch.Tensor) else torch.as_tensor(np.asarray(ob), device=self.device)
-            if o.shape != (N,) or o.dtype.is_floating_point:
-                raise ValueError("Controller.reset_nodes: ob must be an int [%d] array" % N)
-            new = self._start[o.long().clamp(0, self.n_obs - 1)]
-        if where is None:
-            self.node.copy_(new)
-        else:
-            w = where.to(self.device) if isinstance(where, torch.Tensor) else torch.as_tensor(np.asarray(where), device=self.device)
-            if w.shape != (N,) or w.dtype.is_floating_point:
-                raise ValueError("Controller.reset_nodes: where must be a bool / integer [%d] array" % N)
-            self.node.copy_(torch.where(w != 0, new, self.node))
-        return self.node
+    def _native_call(self):
+        """(the C entry point's name, its controller argument) of env.run_controller"""
+        from . import _native
+        return "pomdp_controller_episodes", _native.Controller(action=self.action.data_ptr(), next=self.next.data_ptr(),
+                                                               n_nodes=self.n_nodes, n_obs=self.n_obs, node=self.node.data_ptr())
 
     # ---- building controllers -----------------------------------------------------------------------------------------------
     @classmethod

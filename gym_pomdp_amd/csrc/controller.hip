@@ -4,15 +4,10 @@
 // policy's action read from LDS at the lane's node and the node advanced on the step's own observation; same draws, same
 // sinks (Packed, Narrow, EpisodeReturns).
 // Part of libpomdp_hip.so; built by gym_pomdp_amd/_native.py (hipcc --offload-arch=gfx950 -O3 -std=c++17 -c, one object per file).
-#include "kernels_common.hip.h"
+#include "controller_common.hip.h"
 #include <cstring>
 
 namespace pomdp {
-
-constexpr uint32_t CTRL_MAX_NODES = 4096, CTRL_MAX_EDGES = 16384;      // the header's limits: 4 KB + 32 KB of LDS
-// what the narrow tables hold for an entry the contract refuses: an action that does not fit a byte (255 is out of range for
-// every env, so it stays the invalid action it was — as_tape's rule for a tape byte) and a successor outside [0, n_nodes)
-constexpr uint32_t CTRL_NO_ACTION = 0xFFu, CTRL_NO_NODE = 0xFFFFu;
 
 struct ControllerRef {
     const int32_t *action, *next;
@@ -24,33 +19,6 @@ struct ControllerRef {
 // the launch's dynamic LDS: a halfword per successor and a byte per node — what the controller needs, not what the largest
 // would (36 KB, four workgroups per CU: a 128-node controller leaves the CU to the registers' eight waves per SIMD)
 static inline unsigned ctrl_lds_bytes(const ControllerRef &c) { return (2u * c.n_nodes * c.n_obs + c.n_nodes + 15u) & ~15u; }
-
-// dst[i] = narrow(src[i]), i < count <= ROWS * BLOCK, by the whole workgroup: thread tid takes entries tid, tid + 256, ...  Straight
-// code, no loop: eight rows of 256 entries at a time, their eight loads in flight together (a thread past the table's end reads
-// its last entry and stores nothing), and a group that lies past the end is skipped, so a small table costs a few branches.
-template <int ROWS, class T, class F>
-static __device__ __forceinline__ void stage_narrow(T *dst, const int32_t *__restrict__ src, uint32_t count, F narrow)
-{
-    constexpr int G = 8;
-    static_assert(ROWS % G == 0, "whole groups");
-#pragma unroll
-    for (int g = 0; g < ROWS / G; ++g) {
-        const uint32_t base = (uint32_t)(g * G * BLOCK);
-        if (base < count) {                                                     // workgroup-uniform
-            uint32_t v[G];
-#pragma unroll
-            for (int j = 0; j < G; ++j) {
-                const uint32_t i = base + (uint32_t)(j * BLOCK) + threadIdx.x;
-                v[j] = (uint32_t)src[i < count ? i : count - 1u];
-            }
-#pragma unroll
-            for (int j = 0; j < G; ++j) {
-                const uint32_t i = base + (uint32_t)(j * BLOCK) + threadIdx.x;
-                if (i < count) dst[i] = (T)narrow(v[j]);
-            }
-        }
-    }
-}
 
 // k_steps consecutive pomdp_<env>_step(flags = 0) calls at t0 + s, lane i taking action[node_i] and then moving to
 // next[node_i][ob].  `done` and `node` are read when the launch starts and written when it ends.  Every lane of a wave runs
@@ -163,43 +131,18 @@ static int launch_controller(const typename Env::Params &p, uint32_t *state, uin
 
 } // namespace pomdp
 
-// the env's observation count from its params (what a controller's `next` has a column for); 0 = unknown env
-static inline int64_t env_obs_count(int env, const void *params)
-{
-    switch (env) {
-    case POMDP_ENV_ROCK: return 3;
-    case POMDP_ENV_TAG: return (int64_t)((const pomdp_tag_params *)params)->obs_cells + 1;
-    case POMDP_ENV_BATTLESHIP: return 2;
-    case POMDP_ENV_TIGER: return 3;
-    case POMDP_ENV_NETWORK: return 3;
-    default: return 0;
-    }
-}
-
 extern "C" {
 
 int pomdp_controller_episodes(const pomdp_episode_args *a, const pomdp_controller *c, uint64_t t0, int64_t k_steps, void *stream)
 {
-    if (!a || !a->params || !a->state || !a->done || k_steps < 0 || bad_range(a->n, a->lane0) || (a->lane0 & 3u))
-        return POMDP_E_BADARG;
-    if (!c || !c->action || !c->next || !c->node || a->tape) return POMDP_E_BADARG;
+    if (!c || !c->action || !c->next || !c->node) return POMDP_E_BADARG;
     if (c->n_nodes < 1 || c->n_nodes > (int32_t)CTRL_MAX_NODES || c->n_obs < 1 ||
         (int64_t)c->n_nodes * c->n_obs > (int64_t)CTRL_MAX_EDGES)
         return POMDP_E_BADARG;
+    int rc = controller_episode_args_check(a, k_steps);
+    if (rc) return rc;
     const int64_t n = a->n;
     const bool rets = a->layout == POMDP_LAYOUT_RETURNS;
-    if (rets) {
-        const pomdp_return_stats *st = a->stats;
-        if (!st || !st->acc || !st->cnt || st->pitch < n || !(st->discount == st->discount)) return POMDP_E_BADARG;
-    } else if (a->layout == POMDP_LAYOUT_PACKED || a->layout == POMDP_LAYOUT_NARROW) {
-        if (!a->traj || a->pitch < n || (a->layout == POMDP_LAYOUT_NARROW && a->pitch % 4 != 0)) return POMDP_E_BADARG;
-    } else {
-        return POMDP_E_BADARG;                                          // frozen mode has no 13-byte layouts
-    }
-    // a Packed record (and a Narrow plane) keeps the observation in a byte: Tag's "opponent seen" value is a ctor argument
-    if (!rets && a->env == POMDP_ENV_TAG && (uint32_t)((const pomdp_tag_params *)a->params)->obs_cells > 255u) return POMDP_E_BADPARAMS;
-    int rc = dispatch_env(a->env, a->params, [](auto, const auto &) { return 0; });
-    if (rc) return rc;
     if ((int64_t)c->n_obs != env_obs_count(a->env, a->params)) return POMDP_E_BADARG;
     if (k_steps == 0 || n == 0) return 0;
     uint64_t dbits = 0;

@@ -1336,7 +1336,8 @@ class BatchedEnv(compat.EnvBase):
         """finish_episodes under a policy that reacts to what each lane observes: `steps` consecutive step() calls of an
         auto_reset=False env in one fused loop (pomdp_controller_episodes), lane i taking ctrl.action[ctrl.node[i]] and then
         moving to ctrl.next[ctrl.node[i]][ob] (`ctrl`: a gym_pomdp_amd.Controller of this env; ctrl.node is updated in place,
-        so a later call goes on where this one stopped).  Same draws as step() at the same call counters, same frozen rows,
+        so a later call goes on where this one stopped) — or, under a gym_pomdp_amd.StochasticController, drawing both among
+        the node's candidates (pomdp_stoch_controller_episodes).  Same draws as step() at the same call counters, same frozen rows,
         layouts, `out` / `stats` and return values as finish_episodes; env.done is updated in place.  An entry a
         validate=False controller should not hold — an action out of range, a successor that is no node — is handled as
         include/pomdp_hip.h says and counted in invalid_action_count().  Then ctrl.reset_nodes(where=env.done) followed by
@@ -1362,8 +1363,7 @@ class BatchedEnv(compat.EnvBase):
         args = _native.EpisodeArgs(env=_native.ENV_KIND[self.env_name], layout=0, params=C.addressof(self._params),
                                    state=self._ptrs[0], done=self._ptrs[3], tape=None, traj=None, pitch=0, stats=None,
                                    err=self._ptrs[4], n=n, seed=self._seed, lane0=self.lane_offset, reserved=0)
-        cargs = _native.Controller(action=ctrl.action.data_ptr(), next=ctrl.next.data_ptr(), n_nodes=ctrl.n_nodes, n_obs=ctrl.n_obs,
-                                   node=ctrl.node.data_ptr())
+        entry, cargs = ctrl._native_call()                   # Controller: pomdp_controller_episodes; StochasticController: its own
         with torch.cuda.device(self.device):
             if layout == "returns":
                 if stats is None:
@@ -1385,8 +1385,8 @@ class BatchedEnv(compat.EnvBase):
                 result = out
             t0 = self._t
             self._t = t0 + steps
-            rc = self._lib.pomdp_controller_episodes(C.byref(args), C.byref(cargs), t0, steps, self._stream())
-            _native.check(rc, "pomdp_controller_episodes")
+            rc = getattr(self._lib, entry)(C.byref(args), C.byref(cargs), t0, steps, self._stream())
+            _native.check(rc, entry)
         self.done = self._done_bool
         return result
 

@@ -90,7 +90,8 @@ enum {
 /* id of the word streams of one (seed, lane, t) */
 enum { POMDP_STREAM_STEP = 0, POMDP_STREAM_RESET = 1, POMDP_STREAM_STEP_SPACE = 2,
        POMDP_STREAM_RESET_SPACE = 3, POMDP_STREAM_ACTION = 4, POMDP_STREAM_ROLLOUT = 5, POMDP_STREAM_NEXT = 6,
-       POMDP_STREAM_STEP_LO = 7, POMDP_STREAM_PARTICLE = 8, POMDP_STREAM_TREE = 9 };
+       POMDP_STREAM_STEP_LO = 7, POMDP_STREAM_PARTICLE = 8, POMDP_STREAM_TREE = 9,
+       POMDP_STREAM_CONTROLLER = 10 };
 
 /* env kinds for the generic entry points */
 enum { POMDP_ENV_ROCK = 0, POMDP_ENV_TAG = 1, POMDP_ENV_BATTLESHIP = 2, POMDP_ENV_TIGER = 3, POMDP_ENV_NETWORK = 4 };
@@ -484,6 +485,54 @@ typedef struct pomdp_controller {
 } pomdp_controller;
 int pomdp_controller_episodes(const pomdp_episode_args *a, const pomdp_controller *c,
                               uint64_t t0, int64_t k_steps, void *stream);
+
+/* pomdp_stoch_controller_episodes: pomdp_controller_episodes under a STOCHASTIC finite-state controller — node q draws its
+ * action from psi(a | q) and its successor from eta(q' | q, ob), inside the loop, per lane and per step.  The controller comes
+ * in candidate form: K nodes, B candidate actions per node, D candidate successors per (node, observation), and uint32
+ * thresholds that cut the 32-bit draw into the candidates' shares (the cumulative probabilities, quantised by the caller); the
+ * deterministic controller is B = D = 1.  `a` is read as by pomdp_controller_episodes; the env's own draws are untouched (step s
+ * runs pomdp_<env>_step(flags = 0) at t0 + s).
+ * Draws: at step s lane g = lane0 + i reads block 0 of stream CONTROLLER at (seed, g, t0 + s) — counter (g, t lo, t hi,
+ *   POMDP_STREAM_CONTROLLER << 24), as the PARTICLE and TREE words are built; a block per lane, not shared by a quad.  Word 0
+ *   (.x) is the action draw u_a, word 1 (.y) the successor draw u_n; words 2 and 3 are not used.
+ * Pick, in integers only: the candidate index of a draw u among `cand` candidates with thresholds thr[0 .. cand - 2] is the
+ *   NUMBER of j in [0, cand - 1) with u > thr[j] (strict).  A count: defined for any threshold values, monotone or not, always
+ *   in [0, cand); a threshold 0xFFFFFFFF is never passed, a threshold 0 is passed by every u but 0.  With thresholds
+ *   thr[j] = ceil(2^32 c_j) - 1 of cumulative probabilities c_j, candidate 0 is drawn with probability ceil(2^32 c_0) / 2^32.
+ *   The action drawn at t0 + s is action[q][index of u_a under action_thr[q]]; the successor is next[q][ob][index of u_n under
+ *   next_thr[q][ob]].
+ * Per lane and step, the rules of pomdp_controller_episodes with "action[node]" read as "the action drawn at t0 + s":
+ *   - a live lane steps, records, then moves to the drawn successor — also on the step that ends its episode;
+ *   - a frozen lane does not step; state and node are untouched; its record is the drawn action byte | 1 << 24 — what a
+ *     per-step caller would pass, a function of (seed, lane, t, node) only; nothing is counted;
+ *   - a live lane whose drawn action is outside the env's action range is untouched for that step: record = the action byte,
+ *     (ob, reward, done) = (0, 0, 0), the node unchanged, counted in *a->err, and the returns sink books a step with reward 0;
+ *   - a live lane whose drawn successor is outside [0, n_nodes), or whose observation has no column (Tag with obs_cells < 28):
+ *     the step stands, the node stays, counted;
+ *   - a lane whose incoming node[i] is outside [0, n_nodes) is treated like an out-of-range action on every step: untouched
+ *     and counted while live, node[i] left as it was.
+ * The action byte of a record is the drawn action where that lies in [0, 255] and 255 otherwise.  No table entry, threshold or
+ * node value makes the kernel read outside its tables.
+ * The tables are staged into the workgroup's LDS once per launch, sized by need: actions as bytes, successors as halfwords,
+ * thresholds as 32-bit words — K*B + 4*K*(B-1) + 2*K*n_obs*D + 4*K*n_obs*(D-1) bytes, rounded up to 16, at most
+ * POMDP_STOCH_CONTROLLER_MAX_BYTES (the deterministic controller's largest footprint).
+ * Any n; lane0 a multiple of 4; up to pomdp_fuse_max() steps per launch, `node` read when a launch starts and written when
+ * it ends, so results never depend on the chunking (nor on the sharding: every draw is a function of the global lane).
+ * Refused before anything is enqueued (POMDP_E_BADARG / _BADPARAMS): everything pomdp_controller_episodes refuses; NULL c,
+ * action, next or node; NULL action_thr with n_act_cand > 1, NULL next_thr with n_next_cand > 1; n_nodes outside [1, 4096];
+ * n_act_cand or n_next_cand < 1; a footprint past the limit; n_obs other than the env's observation count.  k_steps == 0 or
+ * n == 0: 0, nothing launched.  The caller's call counter advances by k_steps. */
+#define POMDP_STOCH_CONTROLLER_MAX_BYTES 36864
+typedef struct pomdp_stoch_controller {
+    const int32_t  *action;      /* device [n_nodes][n_act_cand]: the candidate actions of node q */
+    const uint32_t *action_thr;  /* device [n_nodes][n_act_cand - 1]; may be NULL when n_act_cand == 1 */
+    const int32_t  *next;        /* device [n_nodes][n_obs][n_next_cand]: the candidate successors of node q on observation o */
+    const uint32_t *next_thr;    /* device [n_nodes][n_obs][n_next_cand - 1]; may be NULL when n_next_cand == 1 */
+    int32_t  n_nodes, n_obs, n_act_cand, n_next_cand;
+    int32_t *node;               /* device [n], in/out: lane i's current node */
+} pomdp_stoch_controller;
+int pomdp_stoch_controller_episodes(const pomdp_episode_args *a, const pomdp_stoch_controller *c,
+                                    uint64_t t0, int64_t k_steps, void *stream);
 
 /* Steps per fused launch of the C-side drivers above (pomdp_rollout_synthetic with POMDP_FUSE_STEPS, pomdp_collect_*,
  * pomdp_heuristic_steps): a launch's fixed cost (kernel start, table build, drain) is paid once per this many steps.
